@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — simulated peer-message deliveries/s of the GossipSub dissemination
-hot path on MI355X (BASELINE.json metric), plus the relaxation kernel's
-roofline fraction and the CPU oracle's rate on a bounded sample.
+hot path on MI355X (BASELINE.json metric) and the relaxation kernel's roofline
+fraction from the same timed steps. A plain run sets up, warms up, times the
+steps and prints the result line; `--full` adds every other measurement (the
+second graph size, the streamed-output rate, BASELINE's configs, the CPU
+oracle's rate on a bounded sample, the gossip check). `--dump-outputs DIR`
+writes what the last timed step computed as DIR/<name>.npy.
 
 One step = one batch of B messages disseminated over a frozen 1M-peer mesh
 (publish -> flood -> mesh forwarding -> reassembly), inputs resident in HBM.
@@ -14,6 +18,7 @@ exchanges each pass's records over RCCL (strong scaling of one batch, config
 #4).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
 """
 import argparse
 import json
@@ -68,19 +73,26 @@ def parse():
     ap.add_argument("--links", default="5,50,150,40,130", help="stages,bl,bh,ll,lh (topogen.py)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-heartbeats", type=int, default=400)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU oracle sample budget (0=off)")
-    ap.add_argument("--cpu-gossip", type=int, default=0, help="also time the oracle with lazy gossip on (slow)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the companion measurements below (second size, streamed output, configs, "
+                         "CPU baseline, gossip check); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's results as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU oracle sample budget (0=off)")
+    ap.add_argument("--cpu-gossip", type=int, default=0,
+                    help="--full: also time the oracle with lazy gossip on (slow)")
     ap.add_argument("--output-steps", type=int, default=4,
-                    help="with_output: steps timed with the results streamed to host memory (0=off)")
-    ap.add_argument("--configs", type=int, default=1, help="also time BASELINE configs #1-#3 (1 GPU runs)")
+                    help="--full: with_output, steps timed with the results streamed to host memory (0=off)")
+    ap.add_argument("--configs", type=int, default=1,
+                    help="--full: also time BASELINE configs #1-#3 (1 GPU runs; 0=off)")
     ap.add_argument("--mode", choices=("msg", "peer"), default="msg",
                     help="msg: message-sharded ranks (default); peer: peer-partitioned ranks")
     ap.add_argument("--parts", type=int, default=1,
                     help="--mode peer on one process: this many loop-back parts (1 = an RCCL rank of one)")
     ap.add_argument("--also-peers", type=int, default=100_000,
-                    help="second graph size reported beside the headline (metric names 100k & 1M; 0=off)")
+                    help="--full: second graph size reported beside the headline (metric names 100k & 1M; 0=off)")
     ap.add_argument("--gossip-check", type=int, default=64,
-                    help="messages of the 1M-peer gossip-on vs eager-only delivery comparison (0=off)")
+                    help="--full: messages of the 1M-peer gossip-on vs eager-only delivery comparison (0=off)")
     ap.add_argument("--config-traffic-json", default=os.path.join(ROOT, "profiles", "config_traffic_latest.json"),
                     help="per-config HBM bytes from rocprofv3 --pmc passes (scripts/config_pmc.sh + config_traffic.py)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
@@ -360,6 +372,7 @@ def measure(args, sim, peers, world, rank, torch, dist):
         else:
             comm = gossipsim.Comm(local_parts=args.parts)
             sims += [make_sim(args, peers, *sim._bench_links, sim.cfg.c.device)[0] for _ in range(args.parts - 1)]
+            sim._bench_parts = sims[1:]
         sim._bench_comm = comm
 
         def step(i):  # every rank works on the same batch, each over its own peers
@@ -396,6 +409,55 @@ def measure(args, sim, peers, world, rank, torch, dist):
     tot = allreduce(torch, dist, world, [st["deliveries"], st["frag_deliveries"], st["relaxations"],
                                          st["bytes_alg"]], SUM)
     return max_elapsed, st, tot
+
+
+DUMP_BYTES = 60 << 20  # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(args, sim, rank, world):
+    """--dump-outputs: the results of the last timed step, the arrays a caller
+    of the timed path receives through a result sink. The timed steps leave
+    them on the device (collect=False), so that step's schedule runs once more
+    through the same entry point (gs_run, or gs_run_partitioned under --mode
+    peer) with a sink; the simulation is deterministic and the frozen mesh
+    carries no state from batch to batch, so this run computes what the timed
+    one did. Written per (message, sampled peer): latency_ns = t_complete -
+    t_pub in ns (float64, exact below 2^53; -1 where never delivered), hops
+    (float32), and peers = the sampled peer ids (float64): every peer while
+    the files fit DUMP_BYTES, else a sorted sample drawn with a fixed seed."""
+    N, M = args.peers, args.batch
+    last = args.warmup + args.steps - 1
+    n_s = max(1, min(N, DUMP_BYTES // (12 * M + 8)))  # a sampled peer costs M x (8 + 4) bytes and its id
+    cols = np.arange(N) if n_s == N else np.sort(np.random.default_rng(12345).choice(N, n_s, replace=False))
+    lat = np.full((M, n_s), -1.0, np.float64)  # (ranks of --mode peer fill their own peers' columns only)
+    hops = np.zeros((M, n_s), np.float32)
+    never = np.iinfo(np.uint64).max
+
+    def put(m0, t_pub, tc, hp, own=None):
+        # tc / hp [n, peers of `own`]: keep the sampled columns of these rows
+        c = cols if own is None else cols[(cols >= own[0]) & (cols < own[1])] - own[0]
+        dst = slice(None) if own is None else (cols >= own[0]) & (cols < own[1])
+        t = tc[:, c]
+        d = (t - t_pub[:, None]).astype(np.float64)
+        d[t == never] = -1.0
+        lat[m0:m0 + len(t), dst] = d
+        hops[m0:m0 + len(t), dst] = hp[:, c]
+
+    if args.mode == "peer":
+        t_pub, pub, size = gossipsim.shard_messages(last, 0, 1, M, N, args.msg_size)
+        sims = [sim] + [x for x in getattr(sim, "_bench_parts", [])]
+        for part in sim._bench_comm.run_partitioned(sims, (t_pub, pub, size), collect=True):
+            put(0, t_pub, part["t_complete"], part["hops"], own=tuple(int(x) for x in part["peer_range"]))
+    else:
+        t_pub, pub, size = gossipsim.shard_messages(last, rank, world, M, N, args.msg_size)
+        sim.run((t_pub, pub, size), block_msgs=64,
+                on_block=lambda first, tc, hp: put(first, t_pub[first:first + len(tc)], tc, hp))
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    pre = "" if world == 1 else "rank%d_" % rank
+    for name, a in (("latency_ns", lat), ("hops", hops), ("peers", cols.astype(np.float64))):
+        np.save(os.path.join(args.dump_outputs, pre + name + ".npy"), a)
+    return {"dir": args.dump_outputs, "step": last, "msgs": M, "peers_sampled": int(n_s),
+            "arrays": ["latency_ns", "hops", "peers"]}
 
 
 # BASELINE.json configs #1-#3 on one GPU, timed like the headline (inputs in HBM,
@@ -545,7 +607,10 @@ def main():
     max_elapsed, st, tot = steps
     deliveries = tot[0]
     extra = None
-    if args.also_peers and args.also_peers != args.peers and args.mode == "msg":
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args, sim, rank, world)
+    if args.full and args.also_peers and args.also_peers != args.peers and args.mode == "msg":
         sim2, _, _ = make_sim(args, args.also_peers, S, links, local)
         e2, _, tot2 = measure(args, sim2, args.also_peers, world, rank, torch, dist)
         extra = {"peers": args.also_peers, "value": tot2[0] / e2, "ms_per_step": e2 * 1e3 / args.steps}
@@ -599,21 +664,21 @@ def main():
             "pushes_per_relaxation": st["pushes"] / max(1, st["relaxations"])}
 
     wout = None
-    if args.output_steps and args.mode == "msg":
+    if args.full and args.output_steps and args.mode == "msg":
         wout = with_output(args, sim, rank, world)
         (wdt,) = allreduce(torch, dist, world, [wout["ms_per_step"]], dist.ReduceOp.MAX if dist else None)
         wout["value"] = wout["value"] * world * wout["ms_per_step"] / wdt  # job rate at the slowest rank
         wout["ms_per_step"] = wdt
 
     cfg_rates = None
-    if world == 1 and args.configs and args.mode == "msg":
+    if args.full and world == 1 and args.configs and args.mode == "msg":
         cfg_rates = config_rates(args, local)
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0 and args.mode == "msg":
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0 and args.mode == "msg":
         cpu = cpu_baseline(sim, args, S, links, args.cpu_seconds)
     gcheck = None
-    if rank == 0 and world == 1 and args.gossip_check and args.mode == "msg":
+    if args.full and rank == 0 and world == 1 and args.gossip_check and args.mode == "msg":
         gcheck = gossip_check(args, S, links, local, args.gossip_check)
 
     if rank == 0:
@@ -648,6 +713,8 @@ def main():
             "relaxations": int(tot[2]),
             "bytes_alg": int(tot[3]),
             "dist": DIST or None,
+            "full": bool(args.full),
+            "dumped_outputs": dumped,
             "setup_s": t_setup,
             "mesh_epochs": epochs,
             "buckets_per_step": st["buckets"] / max(1, args.steps),

@@ -26,7 +26,7 @@ for s in ${STEPS:-tests smoke bench prof}; do
     probe) step rccl_probe 300 ./scripts/bin/rccl_p2p_probe ;;
     abbatch) step ab_batch 600 python -u scripts/ab_batch.py ${ABB_ARGS:-} ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python bench.py --steps ${BENCH_STEPS:-20} --warmup 3 ;;
+    bench) step bench 600 python bench.py --full --steps ${BENCH_STEPS:-20} --warmup 3 ;;
     prof) step prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py $PROFARGS ;;
     ab) step ab_relax 600 python scripts/ab_relax.py ${AB_ARGS:-} ;;
     ubench) step ubench_mem 300 ./build_tools/ubench_mem ;;

@@ -9,6 +9,6 @@ STEPS="prof" bash scripts/gpu_session.sh || exit $?
 GS_LPULL_DENSE=1 STEPS="pmc" bash scripts/gpu_session.sh || exit $?
 python scripts/pmc_summary.py $OUT/pmc_fetch/run_counter_collection.csv $OUT/pmc_write/run_counter_collection.csv \
   $OUT/pmc_summary.json --traffic-json $OUT/traffic_latest.json --peers 1000000 --batch 1024 > $OUT/pmc_summary.log 2>&1 || exit $?
-timeout -k 10 600 python bench.py --steps 20 --warmup 3 --traffic-json $OUT/traffic_latest.json > $OUT/bench.log 2>&1
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 3 --traffic-json $OUT/traffic_latest.json > $OUT/bench.log 2>&1
 echo "bench rc=$?"
 tail -1 $OUT/bench.log

@@ -23,7 +23,7 @@ for st in ${STEPS:-tests ab cfg c3}; do
     c3) mkdir -p "$OUT/c3prof" && run c3prof 300 env OUT="$OUT/c3prof" bash scripts/c3_prof.sh ;;
     trace) run trace 400 rocprofv3 --kernel-trace -d "$OUT/trace" -o run --output-format csv \
              -- python scripts/config_prof.py ${CFG_NAMES:-c2_10k_F8} ;;
-    bench) run bench 600 python bench.py --steps 20 --warmup 3 ;;
+    bench) run bench 600 python bench.py --full --steps 20 --warmup 3 ;;
   esac
 done
 echo "session done"

@@ -10,5 +10,5 @@ case $rc in 0) ;; *) exit $rc;; esac
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -1 $OUT/smoke.log
 case $rc in 0) ;; *) exit $rc;; esac
-timeout -k 10 800 python bench.py > $OUT/bench.log 2>&1
+timeout -k 10 800 python bench.py --full > $OUT/bench.log 2>&1
 echo "bench rc=$?"

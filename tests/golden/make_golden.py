@@ -4,7 +4,8 @@ Sources of truth, all executed from /root/reference (never copied into the repo)
   * shadow/topogen.py (networkx + PyYAML): GML/YAML for several parameter sets ->
     topogen_*.json  (stage bandwidths, GML edge latencies, host -> stage map).
   * shadow/summary_latency.awk and summary_latency_large.awk: summaries of a
-    synthetic arrival log in the reference's grep format -> awk_*.txt.
+    synthetic arrival log in the reference's grep format -> awk_*.txt; these and
+    shadow/summary_shadowlog.awk on the logs the host tests write -> awk_recorded.json.
   * oracle/gs_oracle.c (this repo): small dissemination fixtures -> oracle_*.npz,
     a regression pin of the oracle across rounds (not a reference pin).
 
@@ -127,6 +128,35 @@ def awk_fixtures():
             print("wrote %s__%s.txt" % (inp, script))
 
 
+def awk_recorded():
+    """awk_recorded.json: the reference's awk summaries of the logs that
+    tests/test_host_cpu.py writes through the product's own log writers, each
+    with the sha256 of the log it summarised (the tests write the log again,
+    check the hash and read the recorded summary). Needs the built library."""
+    import hashlib
+    import pathlib
+    sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"),
+                    os.path.join(ROOT, "dst-libp2p-test-node_amd")]
+    import test_host_cpu as T
+    cases = {
+        "shadow_heartbeat": ("summary_shadowlog", lambda d: T._shadow_log(d)[1]),
+        "latency_log__summary_latency": ("summary_latency", T._emit_awk_fixture),
+        "latency_log__summary_latency_large": ("summary_latency_large", T._emit_awk_fixture),
+        "nim_log": ("summary_latency", lambda d: (T._node_log(d, "nim", 1), str(d / "latencies_nim"))[1]),
+        "streaming_log": ("summary_latency_large", lambda d: (T._streamed_log(d), str(d / "lat"))[1]),
+    }
+    rec = {}
+    for name, (script, write) in cases.items():
+        with tempfile.TemporaryDirectory() as d:
+            log = write(pathlib.Path(d))
+            out = subprocess.check_output(["awk", "-f", os.path.join(REF, script + ".awk"), log]).decode()
+            rec[name] = {"script": script, "input_sha256": hashlib.sha256(open(log, "rb").read()).hexdigest(),
+                         "output": out}
+    with open(os.path.join(HERE, "awk_recorded.json"), "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+    print("wrote awk_recorded.json")
+
+
 def oracle_fixtures():
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import oracle
@@ -157,4 +187,5 @@ def oracle_fixtures():
 if __name__ == "__main__":
     topogen_fixtures()
     awk_fixtures()
+    awk_recorded()
     oracle_fixtures()

@@ -4,10 +4,10 @@ topogen links, run.sh schedule, env surface, arrival-log writer) agree with the
 oracle and the reference's golden artefacts. No device compute is called."""
 import ctypes
 import glob
+import hashlib
 import json
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -19,7 +19,17 @@ import oracle
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 HEADER = os.path.join(ROOT, "include", "gossipsim.h")
-REF_SHADOW = "/root/reference/shadow"
+
+
+def recorded_awk(case, log_path):
+    """The reference's awk summary of `log_path`, as recorded in
+    tests/golden/awk_recorded.json by make_golden.py (which ran the script on a
+    log with this sha256): the log written now must be that log byte for byte,
+    and then the recorded text is what the script prints for it."""
+    rec = json.load(open(os.path.join(GOLDEN, "awk_recorded.json")))[case]
+    assert hashlib.sha256(open(log_path, "rb").read()).hexdigest() == rec["input_sha256"], \
+        "the log differs from the one %s.awk summarised for the fixture" % rec["script"]
+    return rec["output"]
 
 
 def declared_symbols():
@@ -136,11 +146,9 @@ def test_shadow_heartbeat_lines(tmp_path):
                                   tr[u, 2], tr[u, 4], tr[u, 0] - tr[u, 4]]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SHADOW) or not shutil.which("awk"),
-                    reason="reference awk scripts only in the build container")
 def test_shadow_heartbeat_round_trips_through_reference_awk(tmp_path):
     tr, out = _shadow_log(tmp_path)
-    got = subprocess.check_output(["awk", "-f", os.path.join(REF_SHADOW, "summary_shadowlog.awk"), out]).decode()
+    got = recorded_awk("shadow_heartbeat", out)
     s = lambda c: int(tr[:, c].sum())
     m = re.search(r"Total Bytes Received :\s+(\d+)\s+Total Bytes Transferred :\s+(\d+)", got)
     assert m and int(m.group(1)) == s(1) + s(11) and int(m.group(2)) == s(0) + s(10)
@@ -262,12 +270,10 @@ def test_latency_log_matches_reference_grep_format(tmp_path):
     assert open(out).read() == open(os.path.join(GOLDEN, "awk_latencies.txt")).read()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SHADOW) or not shutil.which("awk"),
-                    reason="reference awk scripts only in the build container")
 @pytest.mark.parametrize("script", ["summary_latency", "summary_latency_large"])
 def test_latency_log_round_trips_through_reference_awk(tmp_path, script):
     out = _emit_awk_fixture(tmp_path)
-    got = subprocess.check_output(["awk", "-f", os.path.join(REF_SHADOW, script + ".awk"), out]).decode()
+    got = recorded_awk("latency_log__" + script, out)
     want = open(os.path.join(GOLDEN, "awk_latencies__%s.txt" % script)).read()
     assert got == want
 
@@ -353,12 +359,9 @@ def test_node_log_lines(tmp_path):
     assert len({m for s in ids.values() for m in s}) == 2  # one id per message
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SHADOW) or not shutil.which("awk"),
-                    reason="reference awk scripts only in the build container")
 def test_nim_log_round_trips_through_reference_awk(tmp_path):
     _node_log(tmp_path, "nim", 1)
-    got = subprocess.check_output(["awk", "-f", os.path.join(REF_SHADOW, "summary_latency.awk"),
-                                   str(tmp_path / "latencies_nim")]).decode()
+    got = recorded_awk("nim_log", str(tmp_path / "latencies_nim"))
     assert re.search(r"Total Messages Published :\s+2\b", got) and re.search(r"Total Nodes :\s+3\b", got)
     assert re.search(r"MAX :\s+310\b", got)
 
@@ -433,19 +436,21 @@ def test_streaming_log_equals_grouped_writer(tmp_path, node):
     assert sorted(a) == sorted(b) and len(a) > 0
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SHADOW) or not shutil.which("awk"),
-                    reason="reference awk scripts only in the build container")
-def test_streaming_log_round_trips_through_summary_latency_large(tmp_path):
-    """The streamed log through the reference's summary_latency_large.awk: its
-    per-message "MAX delay" lines equal the per-message maxima of the results
-    (the max_ms of gs_msg_summary), and its message count is the schedule's."""
+def _streamed_log(tmp_path):
     cfg, sched, tc = _oracle_run_for_log()
     log = gossipsim.LogStream(cfg, str(tmp_path / "lat"))
     for q0 in range(0, len(sched), 4):
         log.write(sched[q0:q0 + 4], tc[q0:q0 + 4])
     log.close()
-    got = subprocess.check_output(["awk", "-f", os.path.join(REF_SHADOW, "summary_latency_large.awk"),
-                                   str(tmp_path / "lat")]).decode()
+    return sched, tc
+
+
+def test_streaming_log_round_trips_through_summary_latency_large(tmp_path):
+    """The streamed log through the reference's summary_latency_large.awk: its
+    per-message "MAX delay" lines equal the per-message maxima of the results
+    (the max_ms of gs_msg_summary), and its message count is the schedule's."""
+    sched, tc = _streamed_log(tmp_path)
+    got = recorded_awk("streaming_log", str(tmp_path / "lat"))
     mx = {}
     for line in got.splitlines():
         m = re.match(r"MAX delay for\s+(\d+)\s+is\s+(\d+)", line)
