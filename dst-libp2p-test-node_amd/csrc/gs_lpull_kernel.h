@@ -1788,6 +1788,66 @@ __global__ __launch_bounds__(LC_WAVES * 64) void k_lcomplete(LPullArgs a, uint64
   }
 }
 
+// Completion of rows of single-fragment lanes when only batch-wide values are
+// wanted: the counters and, with `bw`, the batch's deliveries (bw[0] +=) and
+// latest final time (bw[1] = max) for the no-op proof of a lockstep batch. A
+// stream over the logged keys alone: every log entry but the publisher's own
+// (k_lpub: the key is the row's id, time 0) is one delivery whatever its lane,
+// so neither flane (a fifth of k_lcomplete's bytes) nor the scatter through
+// LDS is needed. One wave per row, LS_U x 64 keys in flight per wave.
+constexpr uint32_t LS_U = 8;
+__global__ __launch_bounds__(TB) void k_lsum(LPullArgs a, uint64_t* bw) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t stride = gridDim.x * PULL_WAVES;
+  uint32_t deliv = 0;  // a lane: <= PULL_LMAX / 64 entries of each of < 2^21 rows
+  uint64_t lsum = 0, xmax = 0;
+  uint32_t w = blockIdx.x * PULL_WAVES + wv;
+  uint32_t n = w < a.N ? umin32(a.st[(size_t)w * LP_SW + LP_LOG], a.L) : 0u;
+  while (w < a.N) {
+    const uint32_t wn = w + stride;  // the next row's length while this row streams
+    const uint32_t nn = wn < a.N ? umin32(a.st[(size_t)wn * LP_SW + LP_LOG], a.L) : 0u;
+    const uint64_t* kp = a.keys + (size_t)w * a.L;
+    const uint64_t own = (uint64_t)a.u0 + w;
+    for (uint32_t i0 = 0; i0 < n; i0 += 64 * LS_U) {
+      uint64_t k[LS_U];
+#pragma unroll
+      for (int u = 0; u < (int)LS_U; u++) {
+        const uint32_t i = i0 + u * 64 + lane;
+        k[u] = i < n ? __builtin_nontemporal_load(kp + i) : own;
+      }
+#pragma unroll
+      for (int u = 0; u < (int)LS_U; u++) {
+        const uint64_t x = k[u];
+        if (x == own) continue;
+        const uint64_t trel = x >> a.tshift;
+        // floor(t / 1e6) = floor(floor(t / 64) / 15625): one 32-bit division while t < 2^38
+        const uint64_t ms = (trel >> 38) ? trel / 1000000ull : (uint64_t)((uint32_t)(trel >> 6) / 15625u);
+        deliv++;
+        lsum += ms;
+        xmax = x > xmax ? x : xmax;  // the key orders by time first
+      }
+    }
+    w = wn;
+    n = nn;
+  }
+  const uint64_t dw = wave_sum((uint64_t)deliv);
+  lsum = wave_sum(lsum);
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint64_t y = __shfl_xor(xmax, off);
+    xmax = y > xmax ? y : xmax;
+  }
+  if (lane == 0 && dw) {
+    const uint64_t tmax = xmax >> a.tshift;
+    atomicAdd((unsigned long long*)&a.counters[C_DELIV], (unsigned long long)dw);
+    atomicAdd((unsigned long long*)&a.counters[C_LAT_SUM], (unsigned long long)lsum);
+    atomicMax((unsigned long long*)&a.counters[C_LAT_MAX], (unsigned long long)(tmax / 1000000ull));
+    if (bw) {
+      atomicAdd((unsigned long long*)&bw[0], (unsigned long long)dw);
+      atomicMax((unsigned long long*)&bw[1], (unsigned long long)tmax);
+    }
+  }
+}
+
 // Chunks per row of the pass: 8 when a row has <= 512 lanes (half the LDS,
 // twice the resident waves), else 16. GS_LPULL_CH=16 forces the wide form.
 uint32_t lpull_chunks(uint32_t L) {

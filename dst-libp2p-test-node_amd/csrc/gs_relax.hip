@@ -495,9 +495,14 @@ static void launch_seed(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, uint64
 // lat: also the logged latencies [un][B] u16 into d_lat (GS_WANT_LAT_MS).
 // r0: the batch's rows start at row r0 of the key / log buffers (a batch slice, run_slices)
 // pub / tpub: the batch's publishers and publish times (default d_pub / d_tpub)
+// batch_wide: of the reductions the caller reads only the batch's deliveries and latest
+// final time, d_mstat[0] and [1] (batch_sums tells whether they are written that way)
+static bool batch_sums(const Ctx& c, const Batch& b, bool mstat, bool lat, uint32_t nsl, bool batch_wide) {
+  return c.keys_log && b.FP == 1 && !lat && nsl == 1 && (!mstat || batch_wide);
+}
 static void run_complete(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, bool mstat, bool hist,
                          bool store = true, bool lat = false, size_t r0 = 0, const uint32_t* pub = nullptr,
-                         const uint64_t* tpub = nullptr, uint32_t nsl = 1) {
+                         const uint64_t* tpub = nullptr, uint32_t nsl = 1, bool batch_wide = false) {
   if (!pub) pub = c.d_pub.p;
   if (!tpub) tpub = c.d_tpub.p;
   hipStream_t s = c.stream;
@@ -515,6 +520,13 @@ static void run_complete(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, bool 
     if (mstat) {
       c.d_mstat.alloc((size_t)std::max(c.cfg.batch, nsl * b.B) * MS_COLS);
       GS_HIP(hipMemsetAsync(c.d_mstat.p, 0, (size_t)nsl * b.B * MS_COLS * 8, s));
+    }
+    if (batch_sums(c, b, mstat, lat, nsl, batch_wide)) {  // the logged keys alone (k_lsum)
+      const unsigned grid = (unsigned)std::max<uint64_t>(
+          1, std::min<uint64_t>(((uint64_t)un + PULL_WAVES - 1) / PULL_WAVES, (uint64_t)std::max(1, c.num_cus) * 8));
+      k_lsum<<<grid, TB, 0, s>>>(la, mstat ? c.d_mstat.p : nullptr);
+      GS_HIP(hipGetLastError());
+      return;
     }
     const unsigned grid = (unsigned)std::max<uint64_t>(
         1, std::min<uint64_t>(((uint64_t)un + LC_WAVES - 1) / LC_WAVES,
@@ -2439,11 +2451,15 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
         done = true;
       } else {  // keep the eager result only if gossip provably changes nothing
         const SinkWants sw = sink_wants(sink);
-        run_complete(c, b, 0, N, true, sw.summary, sw.rows() || sw.summary, sw.lat);
-        std::vector<uint64_t> ms((size_t)B * MS_COLS);
+        // a lockstep batch (one rel0): a message has at most N - 1 deliveries, so the batch's
+        // total is reached only when none is undelivered, and the largest of the messages'
+        // latest times is the batch's; the per-message test is then a test of these two
+        const bool bsum = batch_sums(c, b, true, sw.lat, 1, lockstep);
+        run_complete(c, b, 0, N, true, sw.summary, sw.rows() || sw.summary, sw.lat, 0, nullptr, nullptr, 1, lockstep);
+        std::vector<uint64_t> ms(bsum ? 2 : (size_t)B * MS_COLS);
         GS_HIP(hipMemcpyAsync(ms.data(), c.d_mstat.p, ms.size() * 8, hipMemcpyDeviceToHost, s));
         GS_HIP(hipStreamSynchronize(s));
-        if (gossip_noop(b, ms.data(), rel0)) {
+        if (bsum ? ms[0] == (uint64_t)B * (N - 1) && ms[1] < rel0[0] + b.lat_min : gossip_noop(b, ms.data(), rel0)) {
           if (c.traffic) launch_traffic(c, b);
           deliver(c, b, 0, N, sink, i0);
           c.stats.gossip_noop_msgs += B;
