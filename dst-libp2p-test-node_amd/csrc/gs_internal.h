@@ -297,6 +297,7 @@ struct Ctx {
   } ct[2];
   uint32_t ct_par = 0;          // the table set the next batch prepared in line uses
   std::function<void()> pass_poll;  // called by the list pass between groups of passes (the chain ahead)
+  uint64_t run_batch = 0;           // the batch loop's iteration in this run_messages_impl call (GS_LPULL_CAP_BATCHES)
   hipStream_t pass_ms = nullptr;    // churn runs: the passes' stream off the chain's XCDs (GS_PASS_XCDS)
   hipEvent_t pass_ev[2] = {nullptr, nullptr};
   DevBuf<uint8_t> d_gnz;       // [N] the row's IHAVE plane of the built heartbeat is not empty

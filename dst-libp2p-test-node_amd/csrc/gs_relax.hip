@@ -1208,7 +1208,22 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
     const char* gsw = getenv("GS_GOSSIP_SWITCH");
     la.gsw = gsw && *gsw ? (uint32_t)atoi(gsw) : ~0u;
   }
-  const char* cap = getenv("GS_LPULL_CAP");  // test knob: small lists force the overflow re-run
+  // test knobs, read per batch: GS_LPULL_CAP's small lists force the overflow re-run;
+  // GS_LPULL_CAP_BATCHES (comma-separated 0-based indices of the run's batch loop, in run
+  // order: after the class regrouping) keeps the cap to the listed batches
+  const char* cap = getenv("GS_LPULL_CAP");
+  const char* capb = getenv("GS_LPULL_CAP_BATCHES");
+  if (cap && capb && *capb) {
+    bool listed = false;
+    for (const char* q = capb; *q && !listed;) {
+      char* end = nullptr;
+      const unsigned long long v = strtoull(q, &end, 10);
+      listed = end != q && v == c.run_batch;
+      q = end != q ? end : q + 1;
+      while (*q == ',' || *q == ' ') q++;
+    }
+    if (!listed) cap = nullptr;
+  }
   la.ls = ls;
   la.lcap = cap && *cap ? (uint32_t)std::min<long>(std::max(1, atoi(cap)), (long)ls) : ls;
   // 40 KB of LDS per block: 4 blocks (16 waves, 16 rows in flight) resident per
@@ -1995,7 +2010,12 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
   // AH_LEAD epochs ahead of what the GPU finished). The list pass reads only the
   // batch tables, so the chain may overwrite ring slots of the batch whose
   // passes run; a batch that falls back to the push path joins the chain first
-  // and has churn_ring replay its ring slots.
+  // and has churn_ring replay its ring slots. A replay (from epoch 0 up to the
+  // falling-back batch's last epoch) takes the ring and the mesh state back
+  // below the prepared batch's last epoch ah.h1: the prepared batch is then
+  // dropped and prepares in line after the push path's run, as a batch without
+  // a chain ahead does (the seeds and the push path read the ring's offline
+  // bits, so a prepared batch is only good while the ring holds its epochs).
   constexpr uint64_t AH_MARK = 16, AH_LEAD = 192, AH_SLICE = 64;
   struct Ahead {
     bool on = false, joined = false;
@@ -2095,7 +2115,7 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
     ah_pump(false);
   };
   uint64_t i0 = 0;
-  while (i0 < n_msgs) {
+  for (c.run_batch = 0; i0 < n_msgs; c.run_batch++) {
     if (i0 >= slice_skip) {
       uint64_t ie = 0;
       if (try_slices(i0, ie)) {
@@ -2411,6 +2431,17 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
       if (!done) {  // the push path reads the ring: a chain ahead (of this batch or for the next one)
         ah_join();    // may have run past or overwritten this batch's slots, or a replay moved the ring
         churn_ring(c, h_lo, h_hi + c.cfg.churn_horizon);  // (no epochs when current; else runs / replays them)
+        // a replay ended at this batch's last epoch: the ring slots of the prepared batch's later
+        // epochs (its seeds read their offline bits) hold older epochs again and the mesh state is
+        // behind its tables. The prepared batch is dropped and prepares in line (chn_begin into the
+        // other table set, which this batch's list pass has left; churn_ring runs the epochs again).
+        // The join above enqueued the whole chain and churn_ring waited for its stream.
+        if (ah.on && c.churn_state < ah.h1) {
+          if (dbg_ah)
+            fprintf(stderr, "[ah] batch %llu: dropped (the fallback's replay left the ring at epoch %llu of %llu)\n",
+                    (unsigned long long)ah.i0, (unsigned long long)c.churn_state, (unsigned long long)ah.h1);
+          ah.on = false;
+        }
       }
       if (!done) ensure_ring_ell(c, h_lo, h_hi + c.cfg.churn_horizon);  // the push path reads the ELL ring
       if (!done && gossip) ensure_in_lists(c, h_lo, h_hi + c.cfg.churn_horizon);
