@@ -36,13 +36,20 @@
 // Entry (u64): t - (c' * Delta) | hops | src | lane, the key's low (hops |
 // src) bits kept as they are; the host checks the widths fit.
 //
-// IDONTWANT (go preset; template IDW, rows of one fragment):
-// a final lane's key also goes to the dense keys[N][L] table (INF-initialised
-// for such batches; no final log), and the emit step reads the key of the same
-// lane at each mesh neighbour y: y is skipped when its key time + lat(y -> w)
-// <= t. Such batches run with windows no wider than the smallest latency
+// IDONTWANT (go preset; template IDW, rows of single lanes or
+// of fragment groups): a final lane's key also goes to the dense keys[N][L]
+// table (INF-initialised for such batches, padding lanes included; no final
+// log), and the emit step reads the key of the same lane — the same fragment
+// of the same message — at each mesh neighbour y: y is skipped when its key
+// time + lat(y -> w) <= t, t the fragment's arrival at w (not its uplink
+// start). Such batches run with windows no wider than the smallest latency
 // (gs_relax.hip), so only keys final in earlier windows — written by earlier
-// passes, stable — can pass the test.
+// passes, stable — can pass the test. In a fragment group each lane is tested,
+// stored and counted on its own: the lanes of a group can be final in
+// different windows, and their receiver counts differ (the uplink FIFO takes
+// each lane's own count). Not instantiated with IDW: the churn pass (such
+// batches keep the push path), the peer-partitioned pass (it refuses
+// IDONTWANT) and batch slices (IDONTWANT batches run one batch per pass).
 //
 // Arrival record (every batch): the sender's row lists which of its mesh
 // entries receive the lane (all but the source and the publisher, and for
@@ -485,7 +492,6 @@ __device__ __forceinline__ void glp_ihave_ent(const LPullArgs& a, uint64_t* CW, 
 template <int FP, uint32_t CH, bool IDW = false, bool PART = false, bool GOS = false, bool CHN = false>
 __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
   constexpr uint32_t NG = GS_LP_NG, RCH = GS_LP_RCH;
-  static_assert(!IDW || FP == 1, "IDONTWANT on the list pass: rows of single-fragment lanes");
   static_assert(!GOS || !PART, "gossip on the list pass: gs_run's rows");
   static_assert(!CHN || (!IDW && !PART), "churn on the list pass: gs_run's rows (fragment groups included)");
   // row header: the mesh row (frozen mesh) or, under churn, the CSR row (the
@@ -1102,7 +1108,11 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
         } else if constexpr (IDW) {
           // IDONTWANT from y already here: ky + lat(y -> w) <= t_w. The keys of
           // IB mesh entries are loaded before any is tested (one round trip per
-          // IB entries instead of one per entry; CH = 8 rows run at 80 VGPRs)
+          // IB entries instead of one per entry; CH = 8 rows run at 80 VGPRs).
+          // Fragment groups: lane i is one fragment, so a group's lanes read
+          // consecutive keys of y's row (one segment per group); a lane not
+          // final in this window (act false: final earlier, pending or
+          // padding) loads nothing and counts no receiver
           constexpr uint32_t IB = CH == 8 ? 2 : 8;
           const uint64_t tw = x >> a.tshift;
           for (uint32_t k0 = 0; k0 < deg; k0 += IB) {  // wave-uniform: entry k from lane k
@@ -2217,13 +2227,25 @@ void lpull_dispatch_gos(const LPullArgs& a, unsigned grid, hipStream_t s) {
     lpull_dispatch_chn<true>(FP, a, grid, s);
     return;
   }
-  if (a.idw) {  // IDONTWANT (FP == 1: the host sends fragmented IDONTWANT batches to the push path)
+  if (a.idw) {  // IDONTWANT (dense final keys; single lanes or fragment groups)
     if (lpull_chunks(a.L) == 8) {
       k_gsend<8><<<grid, TB, 0, s>>>(a);
-      k_lpull<1, 8, true, false, true><<<grid, TB, 0, s>>>(a);
+      switch (FP) {
+        case 1: k_lpull<1, 8, true, false, true><<<grid, TB, 0, s>>>(a); break;
+        case 2: k_lpull<2, 8, true, false, true><<<grid, TB, 0, s>>>(a); break;
+        case 4: k_lpull<4, 8, true, false, true><<<grid, TB, 0, s>>>(a); break;
+        case 8: k_lpull<8, 8, true, false, true><<<grid, TB, 0, s>>>(a); break;
+        default: k_lpull<16, 8, true, false, true><<<grid, TB, 0, s>>>(a); break;
+      }
     } else {
       k_gsend<16><<<grid, TB, 0, s>>>(a);
-      k_lpull<1, 16, true, false, true><<<grid, TB, 0, s>>>(a);
+      switch (FP) {
+        case 1: k_lpull<1, 16, true, false, true><<<grid, TB, 0, s>>>(a); break;
+        case 2: k_lpull<2, 16, true, false, true><<<grid, TB, 0, s>>>(a); break;
+        case 4: k_lpull<4, 16, true, false, true><<<grid, TB, 0, s>>>(a); break;
+        case 8: k_lpull<8, 16, true, false, true><<<grid, TB, 0, s>>>(a); break;
+        default: k_lpull<16, 16, true, false, true><<<grid, TB, 0, s>>>(a); break;
+      }
     }
     return;
   }
@@ -2253,9 +2275,24 @@ void lpull_dispatch(uint32_t FP, const LPullArgs& a, unsigned grid, hipStream_t 
     lpull_dispatch_chn<false>(FP, a, grid, s);
     return;
   }
-  if (a.idw) {  // FP == 1 (the host sends fragmented IDONTWANT batches to the push path)
-    if (lpull_chunks(a.L) == 8) k_lpull<1, 8, true><<<grid, TB, 0, s>>>(a);
-    else k_lpull<1, 16, true><<<grid, TB, 0, s>>>(a);
+  if (a.idw) {  // IDONTWANT (dense final keys; single lanes or fragment groups)
+    if (lpull_chunks(a.L) == 8) {
+      switch (FP) {
+        case 1: k_lpull<1, 8, true><<<grid, TB, 0, s>>>(a); break;
+        case 2: k_lpull<2, 8, true><<<grid, TB, 0, s>>>(a); break;
+        case 4: k_lpull<4, 8, true><<<grid, TB, 0, s>>>(a); break;
+        case 8: k_lpull<8, 8, true><<<grid, TB, 0, s>>>(a); break;
+        default: k_lpull<16, 8, true><<<grid, TB, 0, s>>>(a); break;
+      }
+      return;
+    }
+    switch (FP) {
+      case 1: k_lpull<1, 16, true><<<grid, TB, 0, s>>>(a); break;
+      case 2: k_lpull<2, 16, true><<<grid, TB, 0, s>>>(a); break;
+      case 4: k_lpull<4, 16, true><<<grid, TB, 0, s>>>(a); break;
+      case 8: k_lpull<8, 16, true><<<grid, TB, 0, s>>>(a); break;
+      default: k_lpull<16, 16, true><<<grid, TB, 0, s>>>(a); break;
+    }
     return;
   }
   if (lpull_chunks(a.L) == 8) {

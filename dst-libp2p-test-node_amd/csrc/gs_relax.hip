@@ -1716,7 +1716,7 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
   const bool gossip = c.cfg.lazy_gossip != 0;
   // the pull path needs rows in LDS and one mesh per batch (churn uses one per
   // epoch: the push path). IDONTWANT batches run on the list pass with dense
-  // final keys when their rows are single-fragment (k_lpull<1, CH, true>),
+  // final keys (k_lpull<FP, CH, true>; rows of fragment groups with bit 128),
   // else on the push path. Lazy gossip runs on the pull path when the batch
   // proves it a no-op (gossip_noop), else the batch is re-run on the push path.
   const bool churn = c.cfg.churn_ppm != 0;  // per-epoch mesh lookups live on the push path
@@ -2349,9 +2349,16 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
     // keys of earlier windows are final and stored before the pass starts
     Batch bw = b;
     if (idw_b) bw.delta = std::min(b.delta, b.lat_min);
-    const bool pull_ok = pull_any && bw.delta >= pull_grain(b.tshift) && (!idw_b || (b.FP == 1 && (variant & 64)));
-    // Lazy gossip inside the list pass (GOS, gs_lpull_kernel.h): rows without
-    // IDONTWANT (fragment groups too: every fragment is gossiped on its own at its
+    // fragmented IDONTWANT batches (rows of fragment groups, each lane tested on its
+    // own) wherever fragmented rows run at all (bit 128); GS_IDW_FRAG_LIST=0 keeps
+    // them on the push path (A/B, per batch). With colliding fragments (defect D8)
+    // only lane 0 of a group is ever final, as without IDONTWANT.
+    const char* ifl_env = getenv("GS_IDW_FRAG_LIST");
+    const bool idw_frag = (variant & 128) && !(ifl_env && *ifl_env && atoi(ifl_env) == 0);
+    const bool pull_ok = pull_any && bw.delta >= pull_grain(b.tshift) &&
+                         (!idw_b || ((variant & 64) && (b.FP == 1 || idw_frag)));
+    // Lazy gossip inside the list pass (GOS, gs_lpull_kernel.h): rows with or
+    // without IDONTWANT (fragment groups too: every fragment is gossiped on its own at its
     // message's heartbeats, as the oracle's sched_gossip) on the frozen mesh, every message's heartbeats
     // the same time after its publish (lockstep), CSR rows narrow enough for a
     // 58-bit target mask, windows no wider than the smallest latency (an IHAVE
