@@ -181,9 +181,10 @@ __device__ __forceinline__ uint32_t sat32(uint64_t x) { return x > 0xFFFFFFFFull
 // Offset of key hi word hx from the emitted window c (window c + k starts at
 // hi word sat32(hlo64 + k * dG)); for the saturated end of the time range only,
 // where the division of the pass does not apply.
-__device__ __forceinline__ uint32_t lp_rof(uint32_t hx, uint64_t hlo64, uint32_t dG, uint32_t K) {
+// hlo = sat32(hlo64) serves: once hlo64 is past 32 bits both sums saturate.
+__device__ __forceinline__ uint32_t lp_rof(uint32_t hx, uint32_t hlo, uint32_t dG, uint32_t K) {
   uint32_t r = 0;
-  for (uint32_t k = 1; k <= K; k++) r += hx >= sat32(hlo64 + (uint64_t)k * dG) ? 1u : 0u;
+  for (uint32_t k = 1; k <= K; k++) r += hx >= sat32((uint64_t)hlo + (uint64_t)k * dG) ? 1u : 0u;
   return r;  // r == K: beyond the ring (an error the host bound rules out)
 }
 
@@ -537,13 +538,48 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
   constexpr uint32_t RW = CHN ? 2 : 1;  // u64 words per record
   const uint64_t* rrec = PART ? a.rpk : a.lrec + pb * NL * RW;
   const uint32_t* rcnt = PART ? a.rcg : a.lcnt + (size_t)pb * a.N;  // indexed by global peer id
-  uint64_t* wrec = a.lrec + nb * NL * RW;
   const uint64_t* runi = CHN ? a.luni + (size_t)pb * a.N : nullptr;
   uint64_t* wuni = CHN ? a.luni + (size_t)nb * a.N : nullptr;
-  uint32_t* wcnt = a.lcnt + (size_t)nb * a.N;
   const uint32_t* lat = a.tables;
-  const uint32_t* sup = a.tables + S * S;
-  const uint32_t* sdn = a.tables + S * S + S;
+  // Scalar registers: every value that is live across the row
+  // loop costs SGPRs, and what does not fit is spilled to VGPR lanes and read
+  // back with v_readlane in the per-row code. So the small row-loop scalars
+  // travel in one word and are unpacked (s_bfe) where they are used, behind an
+  // empty asm that keeps the unpacked values from being hoisted back out of the
+  // loops, and values that follow from others (sup / sdn from tables and S,
+  // tshift from sb, the written halves of the double buffers from the read
+  // ones, window starts from hlo) are derived at their use. Field widths: K <=
+  // LP_KMAX = 12 and cslot < K, lb = bits_for(L) with L <= PULL_LMAX = 1024,
+  // sb = tshift - HOP_BITS with tshift < 32 (lpull_ring refuses other batches),
+  // S <= MAX_STAGES = 16.
+  static_assert(LP_KMAX < 16 && PULL_LMAX <= 1024 && MAX_STAGES < 32, "packed row-loop scalars");
+  enum : uint32_t { PK_K = 0, PK_CS = 4, PK_LB = 8, PK_SB = 12, PK_S = 17, PK_PULL = 22, PK_PUBW = 23, PK_RDIV = 24,
+                    PK_NB = 25, PK_SLICE = 26 };
+  const uint32_t pk = K | cslot << PK_CS | a.lb << PK_LB | a.sb << PK_SB | S << PK_S | (pull ? 1u << PK_PULL : 0u) |
+                      (a.pubw ? 1u << PK_PUBW : 0u) | (rdiv ? 1u << PK_RDIV : 0u) | nb << PK_NB |
+                      (a.rN ? 1u << PK_SLICE : 0u);
+  auto pk_get = [&]() {
+    uint32_t p = pk;
+    asm volatile("" : "+s"(p));
+    return p;
+  };
+  auto pk_f = [](uint32_t p, uint32_t sh, uint32_t bits) { return (p >> sh) & ((1u << bits) - 1u); };
+  // the pass writes the other half of the [2][N] / [2][N][L] double buffers it
+  // reads (PART reads the packed exchange buffers instead)
+  auto wcnt_of = [&](uint32_t p) -> uint32_t* {
+    if constexpr (PART) return a.lcnt + (size_t)pk_f(p, PK_NB, 1) * a.N;
+    else return const_cast<uint32_t*>(rcnt) + (pk_f(p, PK_NB, 1) ? (ptrdiff_t)a.N : -(ptrdiff_t)a.N);
+  };
+  auto wrec_of = [&](uint32_t p) -> uint64_t* {
+    if constexpr (PART) return a.lrec + (size_t)pk_f(p, PK_NB, 1) * ((size_t)a.N * a.L) * RW;
+    else {
+      const ptrdiff_t d = (ptrdiff_t)((size_t)a.N * a.L * RW);
+      return const_cast<uint64_t*>(rrec) + (pk_f(p, PK_NB, 1) ? d : -d);
+    }
+  };
+  // the emit step's time check start + rmax > tmax as start >= tlim
+  const uint64_t tlim = a.rmax > a.tmax ? 0ull : a.tmax - a.rmax + 1;
+  const uint32_t u0 = PART ? a.u0 : 0u;  // (only gs_run_partitioned's parts have a row offset)
   // lazy gossip: does this window hold IHAVE arrivals of the built heartbeat (k_lctl)?
   bool gw = false;
   uint64_t gR = 0;  // that heartbeat, relative to every t_pub
@@ -588,10 +624,8 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   uint64_t* CW = Ls.cw[wv];
   uint16_t* LST = Ls.lst[wv];
-  const uint64_t smask = (1ull << a.sb) - 1;
   const uint32_t hmask = (1u << HOP_BITS) - 1;
   const uint64_t lanelt = (1ull << lane) - 1;
-  const uint64_t lowmask = (1ull << a.tshift) - 1;
   // per state lane j < K: the window its counter slot stands for, as a hi word
   const uint32_t lwin = lane < (int)K ? (uint32_t)(((uint32_t)lane + K - cslot) % K) : 0u;
   const uint32_t lwhi = sat32(hlo64 + (uint64_t)lwin * a.dG);
@@ -631,17 +665,24 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
       // the nearest pending window; cs and kk pass through an empty asm so that
       // the per-slot offsets and tests are computed here, not hoisted out of the
       // row loop (24 more scalars live across every row: SGPR spills)
-      uint32_t cs = cslot, kk = K, mo = ~0u;
-      asm volatile("" : "+s"(cs), "+s"(kk));
+      const uint32_t p0 = pk_get();
+      const uint32_t cs = pk_f(p0, PK_CS, 4), kk = pk_f(p0, PK_K, 4);
+      uint32_t mo = ~0u;
 #pragma unroll
       for (uint32_t j = 0; j < LP_KMAX; j++) {
         if (j >= kk || !s4[j]) continue;
         act |= j == cs;
         mo = umin32(mo, j >= cs ? j - cs : j + kk - cs);
       }
-      const uint32_t mh = mo == ~0u ? ~0u : sat32(hlo64 + (uint64_t)mo * a.dG);
+      // (window c + k starts at sat32(hlo64 + k * dG) = sat32(hlo + k * dG): once hlo64 is past 32 bits both are ~0)
+      const uint32_t mh = mo == ~0u ? ~0u : sat32((uint64_t)hlo + (uint64_t)mo * hspan);
       if (GOS && gw) act |= !((a.rowdone[wl >> 5] >> (wl & 31)) & 1u) && (!CHN || a.gtag[wl] == gbk);
-      if (pull && !act) {
+      if (pk_f(p0, PK_PULL, 1) && !act) {
+        // the counts' base as a value of this block: each of the gathers below sits under
+        // its own lane mask, and the long-lived pointer was read back from its spill lane
+        // in front of every one of them
+        const uint32_t* rcnt0 = rcnt;
+        asm volatile("" : "+s"(rcnt0));
         if constexpr (CHN) {  // CSR rows, 16 entries at a time until the padding
           const uint4* mp = reinterpret_cast<const uint4*>(a.ccol + (size_t)wl * CELL_W);
           for (int g = 0; g < (int)CELL_W / 16 && !act; g++) {
@@ -653,23 +694,23 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
             }
 #pragma unroll
             for (int u = 0; u < 16; u++)
-              if (e[u] != EMPTY) act |= rcnt[e[u] & 0xFFFFFFu] != 0;
+              if (e[u] != EMPTY) act |= rcnt0[e[u] & 0xFFFFFFu] != 0;
             if (e[15] == EMPTY) break;
           }
         } else {
-          const uint4* mp = reinterpret_cast<const uint4*>(a.mesh + (size_t)(a.u0 + wl) * MESH_W);
+          const uint4* mp = reinterpret_cast<const uint4*>(a.mesh + (size_t)(u0 + wl) * MESH_W);
 #pragma unroll
           for (int k = 0; k < (int)MESH_W / 4; k++) {
             const uint4 m = mp[k];
             const uint32_t e[4] = {m.x, m.y, m.z, m.w};
 #pragma unroll
             for (int u = 0; u < 4; u++)
-              if (e[u] != EMPTY) act |= rcnt[e[u] & 0xFFFFFFu] != 0;
+              if (e[u] != EMPTY) act |= rcnt0[e[u] & 0xFFFFFFu] != 0;
           }
         }
       }
       if (!act) {
-        wcnt[wl] = 0;
+        wcnt_of(p0)[wl] = 0;
         nmh = umin32(nmh, mh);
       }
     }
@@ -680,22 +721,23 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
     w = base + (uint32_t)__builtin_ctzll(am) * stride;
     am &= am - 1;
   }
+  const bool pull1 = pk_f(pk_get(), PK_PULL, 1) != 0;
   uint32_t ej = EMPTY, cj = 0, rj = 0, sv = 0;
   uint64_t ro = 0, ro2 = 0;  // PART: offsets of the neighbours' packed records
   if constexpr (CHN) {
     if (w < a.N) {
       ej = a.ccol[(size_t)w * CELL_W + lane];
       rj = a.cpos[(size_t)w * CELL_W + lane];
-      if (pull && ej != EMPTY) {
+      if (pull1 && ej != EMPTY) {
         cj = rcnt[ej & 0xFFFFFFu];
         if (!((runi[ej & 0xFFFFFFu] >> (rj & 63u)) & 1)) cj = 0;  // no record of it is for w
       }
       if (lane < (int)LP_SW) sv = a.st[(size_t)w * LP_SW + lane];
     }
   } else if (w < a.N && lane < (int)MESH_W) {
-    ej = a.mesh[(size_t)(a.u0 + w) * MESH_W + lane];
-    rj = a.rpos[(size_t)(a.u0 + w) * MESH_W + lane];
-    if (pull && ej != EMPTY) {
+    ej = a.mesh[(size_t)(u0 + w) * MESH_W + lane];
+    rj = a.rpos[(size_t)(u0 + w) * MESH_W + lane];
+    if (pull1 && ej != EMPTY) {
       cj = rcnt[ej & 0xFFFFFFu];
       if constexpr (PART) ro = a.roff[ej & 0xFFFFFFu];
     }
@@ -716,15 +758,18 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
         if (lane < (int)LP_SW) sv2 = a.st[(size_t)w2 * LP_SW + lane];
       }
     } else if (w2 < a.N && lane < (int)MESH_W) {  // w2 < N is wave-uniform
-      ej2 = a.mesh[(size_t)(a.u0 + w2) * MESH_W + lane];
-      rj2 = a.rpos[(size_t)(a.u0 + w2) * MESH_W + lane];
+      ej2 = a.mesh[(size_t)(u0 + w2) * MESH_W + lane];
+      rj2 = a.rpos[(size_t)(u0 + w2) * MESH_W + lane];
       sv2 = a.st[(size_t)w2 * LP_SW + lane];
     }
     if (GOS && gw && w2 < a.N) dw2 = a.rowdone[w2 >> 5];
     const uint64_t cand = __ballot(cj != 0);
+    const uint32_t pr = pk_get();  // this row's copy of the packed scalars
+    const bool pullr = pk_f(pr, PK_PULL, 1) != 0;
+    const uint32_t csr = pk_f(pr, PK_CS, 4);
     // entries destined to window c; a count past the capacity means entries were
     // dropped (ERR_LIST, the batch re-runs on k_pull): read only what was written
-    const uint32_t due = umin32(__builtin_amdgcn_readlane(sv, cslot), a.lcap);
+    const uint32_t due = umin32(__builtin_amdgcn_readlane(sv, csr), a.lcap);
     // gossip windows: a row with a lane not yet final may take IWANT answers
     bool gossip_row = GOS && gw && !((dw >> (w & 31)) & 1u) && (!CHN || a.gtag[w] == gbk);
     uint32_t gnfl = 0, goffa = 0;  // CHN: lanes that may take an IHAVE (not final, online at kh, published)
@@ -738,9 +783,9 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
       }
     }
     if (cand == 0 && due == 0 && !gossip_row) {  // nothing to apply, nothing due: the pending windows stay
-      if (lane == 0) wcnt[w] = 0;
-      if (lane < (int)K && sv) nmh = umin32(nmh, lwhi);
-      if (pull && lane < (int)HW && ej2 != EMPTY) {
+      if (lane == 0) wcnt_of(pr)[w] = 0;
+      if (lane < (int)pk_f(pr, PK_K, 4) && sv) nmh = umin32(nmh, lwhi);
+      if (pullr && lane < (int)HW && ej2 != EMPTY) {
         cj2 = rcnt[ej2 & 0xFFFFFFu];
         if constexpr (PART) ro2 = a.roff[ej2 & 0xFFFFFFu];
         if constexpr (CHN) {
@@ -753,7 +798,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
       continue;
     }
     PP_ADD(7, 1);
-    const uint32_t sw = a.stage[a.u0 + w];
+    const uint32_t sw = a.stage[u0 + w];
     // final bits transposed: lane j holds bit q for lane q*64 + j (u16 per lane)
     uint32_t finT = reinterpret_cast<const uint16_t*>(a.fin + (size_t)w * LP_FW)[lane];
     // churn: the row's lanes offline in the records' next epoch (crossing records)
@@ -767,9 +812,14 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
     //    the first neighbour group's record loads are issued: one memory round
     //    trip for both instead of two in a row.
     uint32_t cb = 0;
-    const uint64_t* lst = a.blk + ((size_t)cslot * a.N + w) * a.ls;
-    const uint32_t lmask = (1u << a.lb) - 1;
-    const uint64_t wlok = wlo << a.tshift;
+    const uint64_t* lst = a.blk + ((size_t)csr * a.N + w) * a.ls;
+    // (lane mask, lane bits and the window's key base: unpacked at each of the three places that apply entries)
+    auto apply_entries = [&](const uint64_t (&en)[4]) {
+      const uint32_t pe = pk_get(), lbe = pk_f(pe, PK_LB, 4);
+      lp_apply_entries(CW, en, (1u << lbe) - 1, lbe, wlo << (pk_f(pe, PK_SB, 5) + HOP_BITS), cb);
+    };
+    const uint32_t Sr = pk_f(pr, PK_S, 5), sbr = pk_f(pr, PK_SB, 5), tsr = sbr + HOP_BITS;
+    const uint32_t* supr = lat + Sr * Sr;  // tables: lat [S][S], sup [S], sdn [S]
     uint64_t e[4];
 #pragma unroll
     for (int u = 0; u < 4; u++) {
@@ -782,8 +832,9 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
     //    record that crosses into the next epoch is dropped where w is offline
     //    there (onl; lane `slot`'s bit fetched from lane slot & 63)
     if constexpr (CHN) {
-      if (pull) {
-        const uint32_t sd = sdn[sw];
+      if (pullr) {
+        const uint32_t sd = supr[Sr + sw];
+        const uint64_t lo = wlo - a.delta;  // the window whose records are pulled
         uint64_t cmk = cand;
         while (cmk) {
           uint32_t U[NG], NN[NG], SER[NG], IB0[NG], IB1[NG], LM0[NG], LM1[NG];
@@ -802,10 +853,10 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
             LM0[k] = r < 32 ? (1u << r) - 1u : ~0u;
             LM1[k] = r < 32 ? 0u : (1u << (r - 32)) - 1u;
             NN[k] = bit ? (uint32_t)__builtin_amdgcn_readlane(cj, j) : 0u;
-            const uint32_t su0 = e >> STAGE_SHIFT, su = su0 < S ? su0 : 0u;
-            SER[k] = sup[su];
-            BASE[k] = ((lo + lat[su * S + sw] + (sd > SER[k] ? sd - SER[k] : 0)) << a.tshift) +
-                      ((1ull << a.sb) | U[k]);
+            const uint32_t su0 = e >> STAGE_SHIFT, su = su0 < Sr ? su0 : 0u;
+            SER[k] = supr[su];
+            BASE[k] = ((lo + lat[su * Sr + sw] + (sd > SER[k] ? sd - SER[k] : 0)) << tsr) +
+                      ((1ull << sbr) | U[k]);
             maxn = NN[k] > maxn ? NN[k] : maxn;
           }
           __amdgpu_buffer_rsrc_t RS[NG];
@@ -823,7 +874,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
             }
             if (ent) {
               ent = false;
-              lp_apply_entries(CW, e, lmask, a.lb, wlok, cb);
+              apply_entries(e);
             }
 #pragma unroll
             for (int k = 0; k < (int)NG; k++) {
@@ -832,7 +883,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
               const uint32_t slot = lo32 & LP_LANE_MASK;
               const uint32_t pos = (uint32_t)__popc(rv[k][2] & LM0[k]) + (uint32_t)__popc(rv[k][3] & LM1[k]) + 1u;
               const uint64_t off = (uint64_t)pos * SER[k] + so;
-              const uint64_t nk = BASE[k] + (((off << HOP_BITS) | (lo32 >> LP_HOP_SHIFT)) << a.sb);
+              const uint64_t nk = BASE[k] + (((off << HOP_BITS) | (lo32 >> LP_HOP_SHIFT)) << sbr);
               if (offn) {  // wave-uniform: a record may cross into epoch ks + 1
                 const uint32_t ob = (uint32_t)__shfl((int)onl, (int)(slot & 63u));
                 if (nk >= xBs && ((ob >> (slot >> 6)) & 1u)) ok = false;
@@ -847,8 +898,9 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
       }
     }
     // 2. this pass's candidates from the neighbours' records of window lo
-    if (!CHN && pull) {
-      const uint32_t sd = sdn[sw];
+    if (!CHN && pullr) {
+      const uint32_t sd = supr[Sr + sw];
+      const uint64_t lo = wlo - a.delta;  // the window whose records are pulled
       uint64_t cmk = cand;
       while (cmk) {
         uint32_t U[NG], NN[NG], SER[NG], IB[NG], LB[NG];
@@ -876,14 +928,14 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
           IB[k] = 1u << (LP_IM_SHIFT + r);
           LB[k] = ((1u << r) - 1u) << LP_IM_SHIFT;
           NN[k] = bit ? (uint32_t)__builtin_amdgcn_readlane(cj, j) : 0u;
-          const uint32_t su0 = e >> STAGE_SHIFT, su = su0 < S ? su0 : 0u;  // a missing neighbour's EMPTY: class 0
-          SER[k] = sup[su];
+          const uint32_t su0 = e >> STAGE_SHIFT, su = su0 < Sr ? su0 : 0u;  // a missing neighbour's EMPTY: class 0
+          SER[k] = supr[su];
           // the candidate key less its record-dependent parts: (arrival base
           // << tshift) + (hops 1 | src); a record adds (start offset + FIFO
           // position * ser) << tshift and its hops << sb (no carries: the low
           // fields stay below 2^tshift, the sender checked the time field)
-          BASE[k] = ((lo + lat[su * S + sw] + (sd > SER[k] ? sd - SER[k] : 0)) << a.tshift) +
-                    ((1ull << a.sb) | U[k]);
+          BASE[k] = ((lo + lat[su * Sr + sw] + (sd > SER[k] ? sd - SER[k] : 0)) << tsr) +
+                    ((1ull << sbr) | U[k]);
           maxn = NN[k] > maxn ? NN[k] : maxn;
         }
         __amdgpu_buffer_rsrc_t RS[NG];  // wave-uniform: base = the neighbour's records, NN[k] of them
@@ -909,7 +961,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
             }
           if (ent) {  // the listed entries while the records are in flight
             ent = false;
-            lp_apply_entries(CW, e, lmask, a.lb, wlok, cb);
+            apply_entries(e);
           }
 #pragma unroll
           for (int k = 0; k < (int)NG; k++)
@@ -927,7 +979,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
               const uint32_t pos = (uint32_t)__popc(lo32 & LB[k]) + 1u;
               const uint64_t off = (uint64_t)pos * SER[k] + (rc >> 32);
               // tshift = sb + HOP_BITS: time and hops are one field above src
-              const uint64_t nk = BASE[k] + (((off << HOP_BITS) | (lo32 >> LP_HOP_SHIFT)) << a.sb);
+              const uint64_t nk = BASE[k] + (((off << HOP_BITS) | (lo32 >> LP_HOP_SHIFT)) << sbr);
               if (ok) {
                 atomicMin((unsigned long long*)&CW[slot], (unsigned long long)nk);
                 cb |= 1u << (slot >> 6);
@@ -936,14 +988,14 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
         }
       }
     }
-    if (ent) lp_apply_entries(CW, e, lmask, a.lb, wlok, cb);  // no records
+    if (ent) apply_entries(e);  // no records
     for (uint32_t f0 = 256; f0 < due; f0 += 256) {  // more than 256 entries (rare)
 #pragma unroll
       for (int u = 0; u < 4; u++) {
         const uint32_t f = f0 + u * 64 + lane;
         e[u] = f < due ? lst[f] : ~0ull;
       }
-      lp_apply_entries(CW, e, lmask, a.lb, wlok, cb);
+      apply_entries(e);
     }
     PP_T(tG);
     PP_ADD(1, tG - tA);
@@ -953,15 +1005,15 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
     //     iff CW holds a time <= t_i there; else w sends IWANT and v's answer
     //     (its key's hops + 1, src v) is one more candidate, after window c.
     if constexpr (GOS && CHN) {
-      if (gossip_row) glp_ihave_chn(a, CW, sw, gnfl, wlo, gR, ej, rj, goffa, gB1, lat, sup, sdn, cb, niw, err);
-      if (due) glp_ihave_ent(a, CW, w, sw, finT, lst, due, wlok, lat, sup, sdn, cb, niw, err);
+      if (gossip_row) glp_ihave_chn(a, CW, sw, gnfl, wlo, gR, ej, rj, goffa, gB1, lat, supr, supr + Sr, cb, niw, err);
+      if (due) glp_ihave_ent(a, CW, w, sw, finT, lst, due, wlo << tsr, lat, supr, supr + Sr, cb, niw, err);
     } else if constexpr (GOS) {
-      if (gossip_row) glp_ihave(a, CW, w, sw, finT, wlo, gR, lat, sup, sdn, cb, niw, err);
+      if (gossip_row) glp_ihave(a, CW, w, sw, finT, wlo, gR, lat, supr, supr + Sr, cb, niw, err);
     }
     for (int off = 32; off > 0; off >>= 1) cb |= __shfl_xor(cb, off);
     cb = __builtin_amdgcn_readfirstlane(cb);
     wave_lds_sync();
-    if (pull && lane < (int)HW && ej2 != EMPTY) {  // next row's lists
+    if (pullr && lane < (int)HW && ej2 != EMPTY) {  // next row's lists
       cj2 = rcnt[ej2 & 0xFFFFFFu];
       if constexpr (PART) ro2 = a.roff[ej2 & 0xFFFFFFu];
       if constexpr (CHN) {
@@ -1024,9 +1076,12 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
     // each group of 64 visits only the destination windows present in it)
     uint32_t addl = 0;
     // an EMIT pass's minima all lie in window c, except IWANT answers (GOS)
-    if (!pull && !GOS && npend) err |= ERR_RING;
-    if ((pull || GOS) && npend) {
+    if (!pullr && !GOS && npend) err |= ERR_RING;
+    if ((pullr || GOS) && npend) {
       const uint32_t lmax = a.lcap;
+      const uint32_t pa = pk_get(), K = pk_f(pa, PK_K, 4), cslot = pk_f(pa, PK_CS, 4), lba = pk_f(pa, PK_LB, 4);
+      const uint32_t tsa = pk_f(pa, PK_SB, 5) + HOP_BITS;  // < 32 (lpull_ring): the key's low fields are its low word's
+      const bool rdiv = pk_f(pa, PK_RDIV, 1) != 0;
       for (uint32_t j0 = 0; j0 < npend; j0 += 64) {
         const bool jv = j0 + lane < npend;
         const uint32_t li = jv ? LST[LMAX - 1 - (j0 + lane)] : 0u;
@@ -1040,7 +1095,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
             else if (((uint64_t)q + 1) * hspan <= d) q++;  // widened first: q may be 0xFFFFFFFF
             r = q < K ? q : K;
           } else {
-            r = lp_rof((uint32_t)(x >> 32), hlo64, a.dG, K);
+            r = lp_rof((uint32_t)(x >> 32), hlo, hspan, K);
           }
         }
         if (jv && r >= K) err |= ERR_RING;
@@ -1062,8 +1117,9 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
         if (ap) {
           if (pos >= lmax) err |= ERR_LIST;
           else {
-            const uint64_t toff = (x >> a.tshift) - (wlo + (uint64_t)r * a.delta);
-            a.blk[((size_t)slot * a.N + w) * a.ls + pos] = (toff << (a.tshift + a.lb)) | ((x & lowmask) << a.lb) | li;
+            const uint64_t toff = (x >> tsa) - (wlo + (uint64_t)r * a.delta);
+            a.blk[((size_t)slot * a.N + w) * a.ls + pos] =
+                (toff << (tsa + lba)) | ((uint64_t)((uint32_t)x & ((1u << tsa) - 1u)) << lba) | li;
           }
         }
       }
@@ -1076,9 +1132,11 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
     uint64_t uni = 0;  // churn: the receivers of any of the row's records
     if (cnt) {
       const uint32_t deg = (uint32_t)__popcll(__ballot(ej != EMPTY));  // rows are packed
-      const uint32_t psl = a.rN ? (w / a.rN) * a.B : 0u;  // batch slices: this row's publishers
-      const bool needp = !a.pubw || __builtin_amdgcn_readlane(sv, LP_PUB) != 0;
-      const uint32_t serw = sup[sw];
+      const uint32_t pe = pk_get(), sbe = pk_f(pe, PK_SB, 5), tse = sbe + HOP_BITS, Se = pk_f(pe, PK_S, 5);
+      const uint32_t psl = pk_f(pe, PK_SLICE, 1) ? (w / a.rN) * a.B : 0u;  // batch slices: this row's publishers
+      const bool needp = !pk_f(pe, PK_PUBW, 1) || __builtin_amdgcn_readlane(sv, LP_PUB) != 0;
+      const uint32_t serw = lat[Se * Se + sw];  // sup[sw]
+      uint64_t* const wrec = wrec_of(pe);
       constexpr uint32_t GPW = 64 / FP;
       for (uint32_t g0 = 0; g0 < cnt; g0 += GPW) {
         const uint32_t gi = g0 + (uint32_t)lane / FP;
@@ -1092,12 +1150,12 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
         if (needp) pm = gv ? a.pub[psl + grp] : EMPTY;
         // FP == 1: LST holds only lanes final in window c; a fragment group's
         // other lanes are re-checked
-        const bool act = gv && (FP == 1 || (x != INF64 && ((uint32_t)(x >> 32) - hlo) < hspan)) && a.u0 + w != pm;
-        const uint32_t src = (uint32_t)(x & smask);
+        const bool act = gv && (FP == 1 || (x != INF64 && ((uint32_t)(x >> 32) - hlo) < hspan)) && u0 + w != pm;
+        const uint32_t src = (uint32_t)x & ((1u << sbe) - 1u);  // sb < 32
         uint32_t xm = 0;  // excluded mesh indices: source, publisher (IDW: and IDONTWANT)
         uint64_t im64 = 0;  // churn: the receivers as a mask over the CSR row
         if constexpr (CHN) {  // the mesh of the epoch the lane was received in, less source and publisher
-          const uint32_t kk = kc + ((x >> a.tshift) >= eBc ? 1u : 0u);
+          const uint32_t kk = kc + ((x >> tse) >= eBc ? 1u : 0u);
           const uint64_t mmv = act ? a.cmm[(size_t)w * a.cE + a.cq[grp] + kk] : 0ull;
           uint64_t xm64 = 0;
           for (uint32_t k = 0; k < deg; k++) {  // wave-uniform: entry k from lane k
@@ -1114,7 +1172,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
           // final in this window (act false: final earlier, pending or
           // padding) loads nothing and counts no receiver
           constexpr uint32_t IB = CH == 8 ? 2 : 8;
-          const uint64_t tw = x >> a.tshift;
+          const uint64_t tw = x >> tse;
           for (uint32_t k0 = 0; k0 < deg; k0 += IB) {  // wave-uniform: entry k from lane k
             uint64_t ky[IB];
 #pragma unroll
@@ -1130,7 +1188,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
               const uint32_t e = __builtin_amdgcn_readlane(ej, k);
               const uint32_t y = e & 0xFFFFFFu;
               const bool sk = y == src || y == pm ||
-                              (ky[u] != INF64 && (ky[u] >> a.tshift) + lat[(e >> STAGE_SHIFT) * S + sw] <= tw);
+                              (ky[u] != INF64 && (ky[u] >> tse) + lat[(e >> STAGE_SHIFT) * Se + sw] <= tw);
               xm |= sk ? 1u << k : 0u;
             }
           }
@@ -1142,16 +1200,16 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
         }
         const uint32_t im = CHN ? 0u : ((1u << deg) - 1u) & ~xm;  // the receivers (deg <= MESH_W = 16)
         const uint32_t n = act ? (CHN ? (uint32_t)__popcll(im64) : (uint32_t)__popc(im)) : 0u;
-        const uint64_t start = uplink_start<FP>(a.busy, (size_t)w * a.B + grp, act, x, n, serw, a.tshift);
-        const uint32_t hp = (uint32_t)(x >> a.sb) & hmask;
+        const uint64_t start = uplink_start<FP>(a.busy, (size_t)w * a.B + grp, act, x, n, serw, tse);
+        const uint32_t hp = (uint32_t)(x >> sbe) & hmask;
         if (act) {
           fd++;
           nr += n;
           if (n && hp + 1 >= (1u << HOP_BITS)) err |= ERR_HOPS;
-          if (start - wlo >= (1ull << 32) || (n && start + a.rmax > a.tmax)) err |= ERR_TIME;
+          if (start - wlo >= (1ull << 32) || (n && start >= tlim)) err |= ERR_TIME;
         }
         // act as lane masks: listed (gi < cnt) and not the message's publisher
-        const uint64_t fm = FP == 1 ? (__builtin_amdgcn_uicmp(gi, cnt, 36) & __builtin_amdgcn_uicmp(pm, a.u0 + w, 33))
+        const uint64_t fm = FP == 1 ? (__builtin_amdgcn_uicmp(gi, cnt, 36) & __builtin_amdgcn_uicmp(pm, u0 + w, 33))
                                     : __ballot(act);  // final log: 64 entries per store
         if constexpr (IDW) {
           if (act) a.keys[(size_t)w * LL + i] = x;  // dense: the neighbours' IDONTWANT tests read it
@@ -1198,6 +1256,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
         atomicOr(&a.rowdone[w >> 5], 1u << (w & 31));
     }
     {
+      const uint32_t ps = pk_get(), K = pk_f(ps, PK_K, 4), cslot = pk_f(ps, PK_CS, 4);
       uint32_t nv = sv;  // lane j < K: slot j (window c + lwin), emptied if it is window c's
       if (lane < (int)K) nv = lane == (int)cslot ? 0u : sv + addl;
       if (lane == (int)LP_LOG) nv = logc;
@@ -1208,7 +1267,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
       for (int off = 32; off > 0; off >>= 1) uni |= __shfl_xor(uni, off);
       if (lane == 0) wuni[w] = uni;
     }
-    if (lane == 0) wcnt[w] = ecnt;
+    if (lane == 0) wcnt_of(pk_get())[w] = ecnt;
     nrec += ecnt;
     // 6. LDS back to INF for the next row: the touched chunks. cb passes
     //    through an empty asm so that the chunk tests are recomputed here from
