@@ -218,8 +218,9 @@ struct Ctx {
   size_t h_slms_bytes = 0;
   bool rpos_valid = false;
   bool keys_log = false;       // keys hold the list pull path's final logs (not dense rows): k_lcomplete
+  bool keys_none = false;      // the last batch ran the no-log list pass: keys hold neither rows nor logs
   uint32_t mesh_dmax = 0;      // widest frozen-mesh row (list pull ring bound); 0 = not known
-  DevBuf<uint64_t> d_pctrl;  // [3][4] pass control slots
+  DevBuf<uint64_t> d_pctrl;  // [3][4] pass control slots (gs_run's list pass: and its two batch words, LP_CT_WORDS)
   // list pull path (gs_lpull_kernel.h)
   DevBuf<uint64_t> d_lblk;   // [K][N][L] candidate lists per destination-window slot
   DevBuf<uint32_t> d_lst;    // [N][16] list lengths per destination window, final-log length

@@ -72,6 +72,9 @@ constexpr uint32_t LP_LOG = 15;   // state word holding the final-log length
 // neighbours: only those rows' emit step needs the publishers (LPullArgs::pubw)
 constexpr uint32_t LP_PUB = 12;
 static_assert(LP_KMAX <= LP_PUB && LP_PUB < LP_LOG, "row state words");
+// words of LPullArgs::ctrl after the three pass control slots, kept by a no-log batch
+// (k_lpull<1, CH, .., NOLOG>): its latest final time (ns after t_pub) and its deliveries
+constexpr uint32_t LP_CT_TMAX = 12, LP_CT_DELIV = 13, LP_CT_WORDS = 14;
 // arrival record (u64): start - window_lo (32) | hops (6) | inclusion mask (16) | lane (10)
 constexpr uint32_t LP_IM_SHIFT = 10, LP_HOP_SHIFT = 26, LP_LANE_MASK = (1u << LP_IM_SHIFT) - 1;
 static_assert(MESH_W <= LP_HOP_SHIFT - LP_IM_SHIFT && PULL_LMAX <= (1u << LP_IM_SHIFT) && HOP_BITS == 32 - LP_HOP_SHIFT,
@@ -80,6 +83,7 @@ static_assert(MESH_W <= LP_HOP_SHIFT - LP_IM_SHIFT && PULL_LMAX <= (1u << LP_IM_
 struct LPullArgs {
   uint64_t* keys;       // [N][L] final log during the passes; dense again after k_lfinal
   uint16_t* flane;      // [N][L] lane of each log entry
+                        // (both nullptr in a no-log batch, k_lpull<.., NOLOG>: k_lpub logs nothing)
   uint64_t* busy;       // [N][B] uplink FIFO end per (peer, message), FP > 1
   uint64_t* blk;        // [K][N][ls] candidate lists per destination-window slot
   uint32_t* st;         // [N][LP_SW]
@@ -91,7 +95,7 @@ struct LPullArgs {
   const uint32_t* pub;
   const uint8_t* stage;
   const uint32_t* tables;
-  uint64_t* ctrl;       // [3][4] k_pull's pass control slots
+  uint64_t* ctrl;       // [3][4] k_pull's pass control slots, then LP_CT_TMAX / LP_CT_DELIV
   uint64_t* counters;
   uint64_t delta, tmax;
   uint32_t N, B, L, S, sb, tshift, pass, K, lb, dG;  // lb = lane bits, dG = Delta in key hi-word grains
@@ -490,9 +494,20 @@ __device__ __forceinline__ void glp_ihave_ent(const LPullArgs& a, uint64_t* CW, 
 #ifndef GS_LP_SKIP  // record chunks past a neighbour's count skipped by a scalar branch (off: +1.3 % per step, r06)
 #define GS_LP_SKIP 0
 #endif
-template <int FP, uint32_t CH, bool IDW = false, bool PART = false, bool GOS = false, bool CHN = false>
+// NOLOG (the trailing parameter: profilers match the name by its leading FP, CH):
+// a batch of which the caller reads only counters. The
+// emit step writes no final log; each final adds its latency in ms and its key
+// to two lane accumulators instead (k_lsum's arithmetic), reduced per block at
+// the end of the launch into C_DELIV / C_LAT_SUM / C_LAT_MAX and the batch words
+// ctrl[LP_CT_TMAX] / ctrl[LP_CT_DELIV]. The ms are one 32-bit division, exact
+// while every final time is below 2^38 ns: the host (run_lpull_batch) reads the
+// batch's latest final time and runs a batch that reached 2^38 again with its log.
+template <int FP, uint32_t CH, bool IDW = false, bool PART = false, bool GOS = false, bool CHN = false,
+          bool NOLOG = false>
 __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
   constexpr uint32_t NG = GS_LP_NG, RCH = GS_LP_RCH;
+  static_assert(!NOLOG || (FP == 1 && !IDW && !PART && !GOS && !CHN),
+                "no final log: rows of single-fragment lanes on gs_run's frozen mesh, eager forwarding only");
   static_assert(!GOS || !PART, "gossip on the list pass: gs_run's rows");
   static_assert(!CHN || (!IDW && !PART), "churn on the list pass: gs_run's rows (fragment groups included)");
   // row header: the mesh row (frozen mesh) or, under churn, the CSR row (the
@@ -632,6 +647,9 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
   uint64_t fd = 0, nr = 0, np = 0, nrec = 0;
   uint32_t nmh = ~0u;
   uint32_t err = 0;
+  // NOLOG, per lane: the finals' latencies in ms (every final of FP = 1 rows off the
+  // publisher's own lane is one delivery: fd counts them) and their largest key
+  uint64_t s_ls = 0, s_max = 0;
 #ifdef GS_PULL_PROF
   uint64_t pp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -1027,7 +1045,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
     //    they are in CW.
     PP_T(tR);
     PP_ADD(2, tR - tG);
-    const uint32_t log0 = __builtin_amdgcn_readlane(sv, LP_LOG);
+    const uint32_t log0 = NOLOG ? 0u : __builtin_amdgcn_readlane(sv, LP_LOG);
     uint32_t logc = log0, cnt = 0, npend = 0, nfin = 0;  // the finals are logged in step 4
 #pragma unroll
     for (int q = 0; q < (int)CH; q++) {
@@ -1205,6 +1223,10 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
         if (act) {
           fd++;
           nr += n;
+          if constexpr (NOLOG) {  // k_lsum's ms: floor(t / 1e6) = floor(floor(t / 64) / 15625), t < 2^38
+            s_ls += (uint32_t)((x >> tse) >> 6) / 15625u;
+            s_max = x > s_max ? x : s_max;  // the key orders by time first
+          }
           if (n && hp + 1 >= (1u << HOP_BITS)) err |= ERR_HOPS;
           if (start - wlo >= (1ull << 32) || (n && start >= tlim)) err |= ERR_TIME;
         }
@@ -1213,7 +1235,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
                                     : __ballot(act);  // final log: 64 entries per store
         if constexpr (IDW) {
           if (act) a.keys[(size_t)w * LL + i] = x;  // dense: the neighbours' IDONTWANT tests read it
-        } else {
+        } else if constexpr (!NOLOG) {
           if (act) {
             const uint32_t p =
                 logc + __builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
@@ -1259,7 +1281,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
       const uint32_t ps = pk_get(), K = pk_f(ps, PK_K, 4), cslot = pk_f(ps, PK_CS, 4);
       uint32_t nv = sv;  // lane j < K: slot j (window c + lwin), emptied if it is window c's
       if (lane < (int)K) nv = lane == (int)cslot ? 0u : sv + addl;
-      if (lane == (int)LP_LOG) nv = logc;
+      if (!NOLOG && lane == (int)LP_LOG) nv = logc;
       if (lane <= (int)LP_LOG) a.st[(size_t)w * LP_SW + lane] = nv;
       if (lane < (int)K && nv) nmh = umin32(nmh, lwhi);
     }
@@ -1292,6 +1314,46 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
   fd = wave_sum(fd);
   nr = wave_sum(nr);
   for (int off = 32; off > 0; off >>= 1) err |= __shfl_xor(err, off);
+  if constexpr (NOLOG) {
+    // One flush per block, not per wave: every wave of the grid adds to the same few
+    // words of one cache line, and those atomics serialise at one L2 channel; with this
+    // form's five more of them per wave a launch took 6 % longer than the logged form's
+    // (profiles/r09_nolog). The waves' values go through LDS (each wave's own CW, idle
+    // now) and the block's first thread adds them.
+    s_ls = wave_sum(s_ls);
+    for (int off = 32; off > 0; off >>= 1) {
+      const uint64_t y = __shfl_xor(s_max, off);
+      s_max = y > s_max ? y : s_max;
+    }
+    enum : uint32_t { W_FD, W_LS, W_MAX, W_REC, W_MIN, W_NR, W_NP, W_ERR };
+    if (lane == 0) {
+      CW[W_FD] = fd; CW[W_LS] = s_ls; CW[W_MAX] = s_max; CW[W_REC] = nrec;
+      CW[W_MIN] = nmin; CW[W_NR] = nr; CW[W_NP] = np; CW[W_ERR] = err;
+    }
+    __syncthreads();  // (every wave of the block gets here: the pass has no other exit once its mode is read)
+    if (threadIdx.x != 0) return;
+    uint64_t bfd = 0, bls = 0, bmax = 0, brec = 0, bmin = INF64, bnr = 0, bnp = 0, berr = 0;
+    for (uint32_t q = 0; q < PULL_WAVES; q++) {
+      const uint64_t* v = Ls.cw[q];
+      bfd += v[W_FD]; bls += v[W_LS]; bmax = v[W_MAX] > bmax ? v[W_MAX] : bmax; brec += v[W_REC];
+      bmin = v[W_MIN] < bmin ? v[W_MIN] : bmin; bnr += v[W_NR]; bnp += v[W_NP]; berr |= v[W_ERR];
+    }
+    if (brec) atomicAdd((unsigned long long*)&me[2], (unsigned long long)brec);
+    if (bmin != INF64) atomicMin((unsigned long long*)&me[3], (unsigned long long)bmin);
+    if (bfd) {  // what k_lsum adds for these finals, and the batch words of the no-op proof
+      const uint64_t tl = bmax >> a.tshift;  // the block's latest final time; floor is monotone
+      atomicAdd((unsigned long long*)&a.counters[C_FD], (unsigned long long)bfd);
+      atomicAdd((unsigned long long*)&a.counters[C_DELIV], (unsigned long long)bfd);
+      atomicAdd((unsigned long long*)&a.counters[C_LAT_SUM], (unsigned long long)bls);
+      atomicMax((unsigned long long*)&a.counters[C_LAT_MAX], (unsigned long long)(tl / 1000000ull));
+      atomicAdd((unsigned long long*)&a.ctrl[LP_CT_DELIV], (unsigned long long)bfd);
+      atomicMax((unsigned long long*)&a.ctrl[LP_CT_TMAX], (unsigned long long)tl);
+    }
+    if (bnr) atomicAdd((unsigned long long*)&a.counters[C_R_FWD], (unsigned long long)bnr);
+    if (bnp) atomicAdd((unsigned long long*)&a.counters[C_PUSH], (unsigned long long)bnp);
+    if (berr) atomicOr((unsigned*)&a.counters[C_ERR], (uint32_t)berr);
+    return;
+  }
   if (lane == 0) {
     if (nrec) atomicAdd((unsigned long long*)&me[2], (unsigned long long)nrec);
     if (nmin != INF64) atomicMin((unsigned long long*)&me[3], (unsigned long long)nmin);
@@ -1692,6 +1754,7 @@ __global__ void k_lpub(LPullArgs a, uint32_t Fe) {
     a.keys[(size_t)p * a.L + i] = (uint64_t)(p + a.u0);
     return;
   }
+  if (!a.keys) return;  // no-log batch (the publisher's own key is no delivery)
   const uint32_t pos = atomicAdd(&a.st[(size_t)p * LP_SW + LP_LOG], 1u);
   a.keys[(size_t)p * a.L + pos] = (uint64_t)(p + a.u0);
   a.flane[(size_t)p * a.L + pos] = (uint16_t)i;
@@ -2329,7 +2392,13 @@ void lpull_dispatch_gos(const LPullArgs& a, unsigned grid, hipStream_t s) {
   }
 }
 
-void lpull_dispatch(uint32_t FP, const LPullArgs& a, unsigned grid, hipStream_t s) {
+// nolog: the batch keeps no final log (run_lpull_batch's rule; FP = 1, the plain pass)
+void lpull_dispatch(uint32_t FP, const LPullArgs& a, unsigned grid, hipStream_t s, bool nolog = false) {
+  if (nolog) {
+    if (lpull_chunks(a.L) == 8) k_lpull<1, 8, false, false, false, false, true><<<grid, TB, 0, s>>>(a);
+    else k_lpull<1, 16, false, false, false, false, true><<<grid, TB, 0, s>>>(a);
+    return;
+  }
   if (a.ccol) {  // churn without lazy gossip (rows of fragment groups: FP lanes per message)
     lpull_dispatch_chn<false>(FP, a, grid, s);
     return;

@@ -393,7 +393,7 @@ uint64_t part_begin(Ctx& c, const gs_publish* sched, uint64_t n_msgs) {
   c.part_b = setup_batch(c, sched, 0, n_msgs);
   const Batch& b = c.part_b;
   const uint64_t total = (uint64_t)un * b.L;
-  c.keys_log = false;  // dense rows from here on (gs_relax.hip list pull path leaves logs)
+  c.keys_log = c.keys_none = false;  // dense rows from here on (gs_relax.hip list pull path leaves logs, or nothing)
   GS_HIP(hipMemsetAsync(c.d_keys.p, 0xFF, total * 8, s));
   if (FP > 1) GS_HIP(hipMemsetAsync(c.d_busy.p, 0, (size_t)un * b.B * 8, s));
   GS_HIP(hipMemsetAsync(c.d_fbits.p, 0, (total + 63) / 64 * 8, s));
@@ -724,7 +724,7 @@ bool part_lp_begin(Ctx& c, const gs_publish* sched, uint64_t n_msgs) {
     if (read_counter(c, C_ERR) & ERR_MESH) c.fail(GS_ERANGE, "mesh is not symmetric");
     c.rpos_valid = true;
   }
-  c.keys_log = false;
+  c.keys_log = c.keys_none = false;
   if (b.FP > 1) GS_HIP(hipMemsetAsync(c.d_busy.p, 0, (size_t)un * b.B * 8, s));
   GS_HIP(hipMemsetAsync(c.d_lst.p, 0, (size_t)un * LP_SW * 4, s));
   GS_HIP(hipMemsetAsync(c.d_lfin.p, 0, (size_t)un * LP_FW * 4, s));

@@ -506,6 +506,7 @@ static void run_complete(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, bool 
   if (!pub) pub = c.d_pub.p;
   if (!tpub) tpub = c.d_tpub.p;
   hipStream_t s = c.stream;
+  if (c.keys_none) c.fail(GS_EINVAL, "internal: completion after a no-log list pass (the passes completed the batch)");
   if (lat) c.d_lat.alloc((size_t)un * c.cfg.batch);
   if (c.keys_log) {  // list pull path, results on the device: reduce the final logs
     // (nsl batch slices of un rows each, one launch: block row y = slice y, run_slices)
@@ -813,6 +814,8 @@ static void deliver(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, const gs_r
   if (!sink) return;
   hipStream_t s = c.stream;
   const SinkWants w = sink_wants(sink);
+  if (c.keys_none && (w.rows() || w.lat || w.summary))
+    c.fail(GS_EINVAL, "internal: a sink's results after a no-log list pass");
   if (c.lat_async && w.lat && !w.rows() && !w.summary && sink->on_lat) {
     deliver_lat_async(c, b, un, sink, sink_row0);
     return;
@@ -892,6 +895,7 @@ static RelaxArgs relax_args(Ctx& c, const Batch& b, bool gossip) {
 // Per-peer traffic of the batch just finished (keys final, before the next
 // reset; gs_traffic.h).
 static void launch_traffic(Ctx& c, const Batch& b) {
+  if (c.keys_none) c.fail(GS_EINVAL, "internal: the traffic pass after a no-log list pass");
   const bool gossip = c.cfg.lazy_gossip != 0;
   const RelaxArgs ra = relax_args(c, b, gossip);
   TrafficArgs ta{};
@@ -1105,22 +1109,37 @@ struct Slices {
   const uint32_t* lpub;
 };
 
+// No-log batch (k_lpull<1, CH, .., NOLOG>): the caller reads only
+// counters, so the passes write no final log and complete the batch themselves.
+// on: asked for by the caller (run_messages_impl's rule). After the batch: inexact = a final
+// time reached 2^38 ns, where the passes' 32-bit ms are not k_lsum's (the counters are restored
+// and the caller runs the batch again with its log); else tmax / deliv, the batch's latest
+// final time after t_pub and its deliveries, for the no-op proof of a lockstep batch.
+struct NoLog {
+  bool on = false, inexact = false;
+  uint64_t tmax = 0, deliv = 0;
+};
+constexpr uint64_t NOLOG_TLIM = 1ull << 38;  // (t >> 6) / 15625 in 32 bits
+
 template <class EvFn>
 static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvFn& ev, size_t& n_ev, int dev_cus,
                             bool dense, bool idw, const GosRun* gos = nullptr, const ChnRun* chn = nullptr,
-                            const Slices* sl = nullptr) {
+                            const Slices* sl = nullptr, NoLog* nl = nullptr) {
   const uint32_t N0 = c.cfg.peers, L = b.L;
   const uint32_t N = sl ? sl->S * N0 : N0;  // the pass's rows
   hipStream_t s = c.stream;
   const size_t NL = (size_t)N * L;
+  const bool nolog = nl && nl->on;
+  if (nolog && (dense || idw || gos || chn || sl || b.FP != 1))
+    c.fail(GS_EINVAL, "internal: no-log list pass asked for a batch it cannot take");
   c.d_lrec.alloc((chn ? 4 : 2) * NL);  // churn records are 16 B
   c.d_lcnt.alloc(2 * (size_t)N);
-  c.d_pctrl.alloc(12);
+  c.d_pctrl.alloc(LP_CT_WORDS);
   const uint32_t ls = lpull_stride(b);
   c.d_lblk.alloc((size_t)K * N * ls);
   c.d_lst.alloc((size_t)N * LP_SW);
   c.d_lfin.alloc((size_t)N * LP_FW);
-  c.d_flane.alloc(NL);
+  if (!nolog) c.d_flane.alloc(NL);
   if (!c.rpos_valid) {
     c.d_rpos.alloc((size_t)N0 * MESH_W);
     GS_HIP(hipMemsetAsync(c.d_counters.p + C_ERR, 0, 8, s));
@@ -1139,7 +1158,8 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
   }
   GS_HIP(hipMemsetAsync(c.d_lst.p, 0, (size_t)N * LP_SW * 4, s));
   GS_HIP(hipMemsetAsync(c.d_lfin.p, 0, (size_t)N * LP_FW * 4, s));
-  GS_HIP(hipMemsetAsync(c.d_pctrl.p, 0, 12 * 8, s));  // every slot {lo 0, DONE, 0 records, min INF}
+  // every slot {lo 0, DONE, 0 records, min INF}; the batch's latest final time and deliveries 0
+  GS_HIP(hipMemsetAsync(c.d_pctrl.p, 0, LP_CT_WORDS * 8, s));
   for (int q = 0; q < 3; q++) GS_HIP(hipMemsetAsync(c.d_pctrl.p + q * 4 + 3, 0xFF, 8, s));
   c.d_lp_save.alloc(C_COUNT);
   GS_HIP(hipMemcpyAsync(c.d_lp_save.p, c.d_counters.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
@@ -1156,6 +1176,7 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
     launch_seed(c, b, 0, N, c.d_pctrl.p + 2 * 4 + 3, nullptr, true);
   LPullArgs la{};
   la.keys = c.d_keys.p; la.flane = c.d_flane.p; la.busy = c.d_busy.p; la.blk = c.d_lblk.p;
+  if (nolog) la.keys = nullptr, la.flane = nullptr;  // (k_lpub's sign that no log is kept)
   la.st = c.d_lst.p; la.fin = c.d_lfin.p;
   la.lrec = c.d_lrec.p; la.lcnt = c.d_lcnt.p; la.rpos = c.d_rpos.p;
   la.mesh = c.d_mesh.p; la.pub = c.d_pub.p; la.stage = c.d_stage.p; la.tables = c.d_tables.p;
@@ -1287,7 +1308,7 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
   }
   auto dispatch = [&] {
     if (gos) lpull_dispatch_gos(la, grid, s);
-    else lpull_dispatch(b.FP, la, grid, s);
+    else lpull_dispatch(b.FP, la, grid, s, nolog);
   };
   uint32_t pass = 0;
   for (;;) {
@@ -1306,6 +1327,8 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
     GS_HIP(hipGetLastError());
     GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_pctrl.p, 12 * 8, hipMemcpyDeviceToHost, s));
     GS_HIP(hipMemcpyAsync(c.h_pinned + 12, c.d_counters.p + C_ERR, 8, hipMemcpyDeviceToHost, s));  // same sync
+    if (nolog)  // (and the batch words: final once DONE is read)
+      GS_HIP(hipMemcpyAsync(c.h_pinned + 13, c.d_pctrl.p + LP_CT_TMAX, 16, hipMemcpyDeviceToHost, s));
     if (c.pass_poll) c.pass_poll();  // (while these passes run: the next batch's epoch chain is enqueued)
     GS_HIP(hipStreamSynchronize(s));
     static const bool dbg_pass = getenv("GS_DEBUG_PASSES") != nullptr;
@@ -1325,7 +1348,26 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
     GS_HIP(hipMemcpyAsync(c.d_counters.p, c.d_lp_save.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
     return false;
   }
+  static_assert(LP_CT_DELIV == LP_CT_TMAX + 1 && 13 + 2 <= H_PINNED_WORDS, "the batch words' host copy");
+  static const bool dbg_comp = getenv("GS_DEBUG_COMPLETION") != nullptr;
+  if (nolog && c.h_pinned[13] >= NOLOG_TLIM) {  // the in-pass ms were not exact: restored as after an overflow
+    GS_HIP(hipMemcpyAsync(c.d_counters.p, c.d_lp_save.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
+    nl->inexact = true;
+    if (dbg_comp)
+      fprintf(stderr, "[lp] batch %llu: no-log pass discarded (a final time >= 2^38 ns)\n",
+              (unsigned long long)c.run_batch);
+    return false;
+  }
   c.stats.list_pull_batches++;
+  if (dbg_comp)
+    fprintf(stderr, "[lp] batch %llu: completion %s\n", (unsigned long long)c.run_batch,
+            nolog ? "in-pass (no log)" : idw ? "dense keys (idontwant)" : dense ? "dense rows (k_lfinal)" : "final log");
+  if (nolog) {  // nothing to complete: no log was written, the counters are added
+    nl->tmax = c.h_pinned[13];
+    nl->deliv = c.h_pinned[14];
+    c.keys_none = true;
+    return true;
+  }
   if (idw) return true;  // the final keys are dense rows already
   if (dense) {  // a sink, the traffic pass or a fragment group needs [N][L] rows
     k_lfinal<<<grid, TB, 0, s>>>(la);
@@ -1852,7 +1894,7 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
     c.d_keys.alloc(NR * g.L);
     if (g.FP > 1) c.d_busy.alloc(NR * Bc);
     auto fresh = [&] {  // per-run state of the group's pass
-      c.keys_log = false;
+      c.keys_log = c.keys_none = false;
       if (g.FP > 1) GS_HIP(hipMemsetAsync(c.d_busy.p, 0, NR * Bc * 8, s));
     };
     const SinkWants sw = sink_wants(sink);
@@ -2214,7 +2256,7 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
     }
     const uint64_t total = (uint64_t)N * L;
     auto reset = [&](uint32_t v, bool with_gossip, bool dense_keys = true) {  // fresh keys and bucket state
-      c.keys_log = false;
+      c.keys_log = c.keys_none = false;
       if (dense_keys) GS_HIP(hipMemsetAsync(c.d_keys.p, 0xFF, total * 8, s));  // the list pull path needs none
       if (FP > 1) GS_HIP(hipMemsetAsync(c.d_busy.p, 0, (size_t)N * B * 8, s));
       if (v & 32) return;
@@ -2398,6 +2440,7 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
       return true;
     };
     bool done = false;
+    NoLog nl;  // the eager batch ran the no-log list pass (set below)
     if (chn) {  // churn on the list pass; a list overflow falls back to the push path
       uint32_t lb = 0;
       Batch bc = b;
@@ -2471,7 +2514,23 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
         // IDONTWANT batches keep their final keys dense all along
         const SinkWants sw = sink_wants(sink);
         const bool dense = !idw_b && (sw.rows() || sw.summary || c.traffic || getenv("GS_LPULL_DENSE"));
-        if (!K || !run_lpull_batch(c, bw, K, lb, ev, n_ev, dev_cus, dense, idw_b)) {
+        // No log (the passes complete the batch) exactly when nothing will read a per-message
+        // value: no sink wants, no traffic pass, rows of single-fragment lanes on the frozen
+        // mesh without IDONTWANT, and with lazy gossip a lockstep batch, whose no-op proof
+        // needs the batch's deliveries and latest final time only (batch_sums). The passes'
+        // 32-bit ms need every final time below 2^38 ns: checked on the batch's latest final
+        // time after its passes (NoLog::inexact). GS_LPULL_SUM=0 (A/B, per batch): the log and k_lsum.
+        const char* nl_env = getenv("GS_LPULL_SUM");
+        nl.on = K && !dense && !sw.lat && !idw_b && !churn && b.FP == 1 && (!gossip || lockstep) &&
+                !(nl_env && *nl_env && atoi(nl_env) == 0);
+        bool lp_ok =
+            K && run_lpull_batch(c, bw, K, lb, ev, n_ev, dev_cus, dense, idw_b, nullptr, nullptr, nullptr, &nl);
+        if (!lp_ok && nl.inexact) {  // the same pass again with its log (k_lsum's 64-bit ms)
+          nl = NoLog{};
+          lp_ok = run_lpull_batch(c, bw, K, lb, ev, n_ev, dev_cus, dense, idw_b);
+        }
+        if (!lp_ok) {
+          nl.on = false;
           if (K && getenv("GS_REQUIRE_LPULL")) c.fail(GS_EUNSUPPORTED, "list pull overflow (GS_REQUIRE_LPULL)");
           if (idw_b) {  // k_pull has no IDONTWANT: the push path takes the batch
             push_run(variant & ~32u, false);
@@ -2485,19 +2544,25 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
       }
       if (!gossip) {
         if (c.traffic) launch_traffic(c, b);
-        launch_complete(c, b, 0, N, sink, i0);
+        if (!nl.on) launch_complete(c, b, 0, N, sink, i0);  // (a no-log batch: the passes completed it)
         done = true;
       } else {  // keep the eager result only if gossip provably changes nothing
         const SinkWants sw = sink_wants(sink);
         // a lockstep batch (one rel0): a message has at most N - 1 deliveries, so the batch's
         // total is reached only when none is undelivered, and the largest of the messages'
         // latest times is the batch's; the per-message test is then a test of these two
-        const bool bsum = batch_sums(c, b, true, sw.lat, 1, lockstep);
-        run_complete(c, b, 0, N, true, sw.summary, sw.rows() || sw.summary, sw.lat, 0, nullptr, nullptr, 1, lockstep);
-        std::vector<uint64_t> ms(bsum ? 2 : (size_t)B * MS_COLS);
-        GS_HIP(hipMemcpyAsync(ms.data(), c.d_mstat.p, ms.size() * 8, hipMemcpyDeviceToHost, s));
-        GS_HIP(hipStreamSynchronize(s));
-        if (bsum ? ms[0] == (uint64_t)B * (N - 1) && ms[1] < rel0[0] + b.lat_min : gossip_noop(b, ms.data(), rel0)) {
+        bool noop;
+        if (nl.on) {  // the two values came with the last pass group's control words
+          noop = nl.deliv == (uint64_t)B * (N - 1) && nl.tmax < rel0[0] + b.lat_min;
+        } else {
+          const bool bsum = batch_sums(c, b, true, sw.lat, 1, lockstep);
+          run_complete(c, b, 0, N, true, sw.summary, sw.rows() || sw.summary, sw.lat, 0, nullptr, nullptr, 1, lockstep);
+          std::vector<uint64_t> ms(bsum ? 2 : (size_t)B * MS_COLS);
+          GS_HIP(hipMemcpyAsync(ms.data(), c.d_mstat.p, ms.size() * 8, hipMemcpyDeviceToHost, s));
+          GS_HIP(hipStreamSynchronize(s));
+          noop = bsum ? ms[0] == (uint64_t)B * (N - 1) && ms[1] < rel0[0] + b.lat_min : gossip_noop(b, ms.data(), rel0);
+        }
+        if (noop) {
           if (c.traffic) launch_traffic(c, b);
           deliver(c, b, 0, N, sink, i0);
           c.stats.gossip_noop_msgs += B;
