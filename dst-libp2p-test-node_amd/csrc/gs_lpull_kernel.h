@@ -476,9 +476,12 @@ __device__ __forceinline__ void glp_ihave_ent(const LPullArgs& a, uint64_t* CW, 
   }
 }
 
-// Record step: groups of NG = 4 neighbours, RCH = 2 chunks of 64 records each
-// per iteration (8 loads in flight per lane; 8 x 64 measured 2 % slower,
-// profiles/r03_v1/ab_record_groups.txt). GS_LP_NG / GS_LP_RCH: A/B builds.
+// Record step: NG = 4 neighbours, RCH = 2 chunks of 64 records each (8 loads in
+// flight per lane; 8 x 64 measured 2 % slower,
+// profiles/r03_v1/ab_record_groups.txt), as NG streams of RCH register slots
+// on single-fragment rows (GS_LP_STREAM) and as groups loaded,
+// awaited and processed together elsewhere. GS_LP_NG / GS_LP_RCH: A/B builds
+// of either form.
 #ifndef GS_LP_NG
 #define GS_LP_NG 4
 #endif
@@ -491,7 +494,10 @@ __device__ __forceinline__ void glp_ihave_ent(const LPullArgs& a, uint64_t* CW, 
 #ifndef GS_LP_RCH
 #define GS_LP_RCH 2
 #endif
-#ifndef GS_LP_SKIP  // record chunks past a neighbour's count skipped by a scalar branch (off: +1.3 % per step, r06)
+#ifndef GS_LP_STREAM  // the non-churn record step as streams (1) or as load-all, wait-all, process-all groups (0)
+#define GS_LP_STREAM 1
+#endif
+#ifndef GS_LP_SKIP  // (groups only) record chunks past a neighbour's count skipped by a scalar branch (off: +1.3 % per step, r06)
 #define GS_LP_SKIP 0
 #endif
 // NOLOG (the trailing parameter: profilers match the name by its leading FP, CH):
@@ -506,6 +512,9 @@ template <int FP, uint32_t CH, bool IDW = false, bool PART = false, bool GOS = f
           bool NOLOG = false>
 __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
   constexpr uint32_t NG = GS_LP_NG, RCH = GS_LP_RCH;
+  // (fragment groups keep the grouped record step: they sit at their VGPR limit, and the
+  // streamed form's two per-lane table values cost every FP > 1 instantiation scratch)
+  constexpr bool STREAM = GS_LP_STREAM != 0 && FP == 1;
   static_assert(!NOLOG || (FP == 1 && !IDW && !PART && !GOS && !CHN),
                 "no final log: rows of single-fragment lanes on gs_run's frozen mesh, eager forwarding only");
   static_assert(!GOS || !PART, "gossip on the list pass: gs_run's rows");
@@ -763,6 +772,12 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
   }
   uint32_t dw = 0;  // gossip windows: the row-done word of row w (every lane reads it)
   if (GOS && gw && w < a.N) dw = a.rowdone[w >> 5];
+  // streamed record step: the row's stage travels with its header, so that the
+  // row's table values are loaded before anything else of the row
+  uint32_t swh = 0;
+  if constexpr (STREAM && !CHN) {
+    if (w < a.N) swh = a.stage[u0 + w];
+  }
   for (; w < a.N; w = wn) {
     PP_T(tA);
     wn = am ? base + (uint32_t)__builtin_ctzll(am) * stride : a.N;  // the next active row
@@ -781,6 +796,10 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
       sv2 = a.st[(size_t)w2 * LP_SW + lane];
     }
     if (GOS && gw && w2 < a.N) dw2 = a.rowdone[w2 >> 5];
+    uint32_t swh2 = 0;
+    if constexpr (STREAM && !CHN) {
+      if (w2 < a.N) swh2 = a.stage[u0 + w2];
+    }
     const uint64_t cand = __ballot(cj != 0);
     const uint32_t pr = pk_get();  // this row's copy of the packed scalars
     const bool pullr = pk_f(pr, PK_PULL, 1) != 0;
@@ -810,13 +829,13 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
           if (!((runi[ej2 & 0xFFFFFFu] >> (rj2 & 63u)) & 1)) cj2 = 0;
         }
       }
-      ej = ej2; rj = rj2; cj = cj2; sv = sv2; ro = ro2; dw = dw2;
+      ej = ej2; rj = rj2; cj = cj2; sv = sv2; ro = ro2; dw = dw2; swh = swh2;
       PP_T(tS);
       PP_ADD(0, tS - tA);
       continue;
     }
     PP_ADD(7, 1);
-    const uint32_t sw = a.stage[u0 + w];
+    const uint32_t sw = STREAM && !CHN ? swh : a.stage[u0 + w];
     // final bits transposed: lane j holds bit q for lane q*64 + j (u16 per lane)
     uint32_t finT = reinterpret_cast<const uint16_t*>(a.fin + (size_t)w * LP_FW)[lane];
     // churn: the row's lanes offline in the records' next epoch (crossing records)
@@ -916,11 +935,130 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
       }
     }
     // 2. this pass's candidates from the neighbours' records of window lo
+    // streamed form: lane j's neighbour's serialisation time and its latency to
+    // w, read from the tables once per row (lanes without a neighbour: class 0)
+    uint32_t serj = 0, latj = 0;
+    if constexpr (STREAM && !CHN) {
+      if (pullr) {
+        const uint32_t su0 = ej >> STAGE_SHIFT, su = su0 < Sr ? su0 : 0u;
+        serj = supr[su];
+        latj = lat[su * Sr + sw];
+      }
+    }
+    // one record rc of a neighbour (ib: w's bit in its inclusion mask, lbm: the
+    // bits below it, ser, base: the neighbour's constants) relaxes its lane in CW
+    auto relax_rec = [&](uint64_t rc, uint32_t ib, uint32_t lbm, uint32_t ser, uint64_t base) {
+      const uint32_t lo32 = (uint32_t)rc;
+      // w receives it iff its bit of the inclusion mask is set (no
+      // record reads 0: no bit), at FIFO position 1 + the receivers
+      // before it; the time field cannot overflow (the sender checked
+      // start + rmax)
+      const bool ok = (lo32 & ib) != 0;
+      const uint32_t slot = lo32 & LP_LANE_MASK;
+      const uint32_t pos = (uint32_t)__popc(lo32 & lbm) + 1u;
+      const uint64_t off = (uint64_t)pos * ser + (rc >> 32);
+      // tshift = sb + HOP_BITS: time and hops are one field above src
+      const uint64_t nk = base + (((off << HOP_BITS) | (lo32 >> LP_HOP_SHIFT)) << sbr);
+      if (ok) {
+        atomicMin((unsigned long long*)&CW[slot], (unsigned long long)nk);
+        cb |= 1u << (slot >> 6);
+      }
+    };
     if (!CHN && pullr) {
       const uint32_t sd = supr[Sr + sw];
       const uint64_t lo = wlo - a.delta;  // the window whose records are pulled
       uint64_t cmk = cand;
-      while (cmk) {
+      if constexpr (STREAM) {
+        // Streamed form (GS_LP_STREAM): NG neighbour contexts in scalar
+        // registers, each streaming its neighbour's 64-record chunks through
+        // its own RCH register slots. A context's turn processes its slots,
+        // steps to the neighbour's next chunks or, when none is left, takes the
+        // next candidate of cmk, and issues the slots' loads again at once: the
+        // loads of the other NG - 1 contexts stay in flight meanwhile (counted
+        // vmcnt), and a row costs the chunk slots its neighbours fill, not the
+        // longest neighbour's iterations per group of NG. The stream's place is
+        // the descriptor itself: base P and the bytes REM from P to the
+        // neighbour's last record, so every load has the same lane offset. A
+        // context without a neighbour has REM <= 0: its bounds-checked loads
+        // read 0 without a memory request, which no record is. The turn is per
+        // context, not per slot, because the RCH slots share the context's
+        // constants (IB, LB, SER, BASE): the refill waits for both.
+        uint32_t SER[NG], IB[NG], LB[NG];
+        int32_t REM[NG];
+        uint64_t BASE[NG], P[NG];
+        uint64_t rec[NG][RCH];
+        constexpr int32_t ADV = (int32_t)(64 * RCH * 8);  // the bytes of one turn
+        uint32_t sds = 0;  // sd as a scalar, read once the first loads are issued
+        // context k takes the next candidate neighbour (none left: no records):
+        // first what its loads need, the stream's place and w's bits ...
+        auto take = [&](int k) -> int {
+          const uint64_t bit = cmk & (~cmk + 1);
+          cmk ^= bit;
+          const int j = bit ? (int)__builtin_ctzll(bit) : 0;
+          const uint32_t u = __builtin_amdgcn_readlane(ej, j) & 0xFFFFFFu;
+          if constexpr (PART)
+            P[k] = (uint64_t)(rrec + (((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(ro >> 32), j) << 32) |
+                                      (uint32_t)__builtin_amdgcn_readlane((uint32_t)ro, j)));
+          else
+            P[k] = (uint64_t)(rrec + (uint64_t)u * LL);
+          // w's bit in the record's inclusion mask, and the bits below it
+          const uint32_t r = __builtin_amdgcn_readlane(rj, j);
+          IB[k] = 1u << (LP_IM_SHIFT + r);
+          LB[k] = ((1u << r) - 1u) << LP_IM_SHIFT;
+          REM[k] = bit ? (int32_t)(__builtin_amdgcn_readlane(cj, j) * 8u) : 0;
+          return j;
+        };
+        // ... then what its records' keys need: the neighbour's table values from
+        // its lane j (a table load here would wait for every record load in
+        // flight) and the candidate key less its record-dependent parts (see the
+        // loop below)
+        auto take_key = [&](int k, int j) {
+          SER[k] = __builtin_amdgcn_readlane(serj, j);
+          BASE[k] = ((lo + __builtin_amdgcn_readlane(latj, j) + (sds > SER[k] ? sds - SER[k] : 0)) << tsr) +
+                    ((1ull << sbr) | (__builtin_amdgcn_readlane(ej, j) & 0xFFFFFFu));
+        };
+        // bounds-checked buffer loads of context k's slots: past the neighbour's
+        // records they read 0 (a forwarding sender has hops >= 1)
+        auto issue = [&](int k) {
+          const __amdgpu_buffer_rsrc_t rs =
+              __builtin_amdgcn_make_buffer_rsrc((void*)P[k], (short)0, REM[k] > 0 ? REM[k] : 0, 0x00020000);
+#pragma unroll
+          for (int cc = 0; cc < (int)RCH; cc++) {
+            const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, (uint32_t)(cc * 64 + lane) * 8u, 0, 0);
+            rec[k][cc] = ((uint64_t)v[1] << 32) | v[0];
+          }
+        };
+        if (cmk) {
+          // wave-uniform and branch-free, as the loop below sets its groups up
+          int J[NG];
+#pragma unroll
+          for (int k = 0; k < (int)NG; k++) J[k] = take(k);
+#pragma unroll
+          for (int k = 0; k < (int)NG; k++) issue(k);
+          ent = false;  // the listed entries and the table values while the first records are in flight
+          apply_entries(e);
+          sds = __builtin_amdgcn_readfirstlane(sd);
+#pragma unroll
+          for (int k = 0; k < (int)NG; k++) take_key(k, J[k]);
+          bool more;
+          do {
+            more = false;
+#pragma unroll
+            for (int k = 0; k < (int)NG; k++) {
+              if (REM[k] > 0) {  // wave-uniform (a context without a neighbour holds no record); the loads stay outside
+#pragma unroll
+                for (int cc = 0; cc < (int)RCH; cc++) relax_rec(rec[k][cc], IB[k], LB[k], SER[k], BASE[k]);
+                REM[k] -= ADV;
+                P[k] += (uint64_t)ADV;
+                if (REM[k] <= 0 && cmk) take_key(k, take(k));
+              }
+              issue(k);
+              more |= REM[k] > 0;
+            }
+          } while (more);  // (what is in flight now is past every neighbour's records)
+        }
+      }
+      while (!STREAM && cmk) {
         uint32_t U[NG], NN[NG], SER[NG], IB[NG], LB[NG];
         uint64_t BASE[NG], RO[NG];
         uint32_t maxn = 0;
@@ -986,22 +1124,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
 #pragma unroll
             for (int cc = 0; cc < (int)RCH; cc++) {
               if (GS_LP_SKIP && i0 + cc * 64 >= NN[k]) continue;  // (nothing loaded: no record)
-              const uint64_t rc = rec[k][cc];
-              const uint32_t lo32 = (uint32_t)rc;
-              // w receives it iff its bit of the inclusion mask is set (no
-              // record reads 0: no bit), at FIFO position 1 + the receivers
-              // before it; the time field cannot overflow (the sender checked
-              // start + rmax)
-              const bool ok = (lo32 & IB[k]) != 0;
-              const uint32_t slot = lo32 & LP_LANE_MASK;
-              const uint32_t pos = (uint32_t)__popc(lo32 & LB[k]) + 1u;
-              const uint64_t off = (uint64_t)pos * SER[k] + (rc >> 32);
-              // tshift = sb + HOP_BITS: time and hops are one field above src
-              const uint64_t nk = BASE[k] + (((off << HOP_BITS) | (lo32 >> LP_HOP_SHIFT)) << sbr);
-              if (ok) {
-                atomicMin((unsigned long long*)&CW[slot], (unsigned long long)nk);
-                cb |= 1u << (slot >> 6);
-              }
+              relax_rec(rec[k][cc], IB[k], LB[k], SER[k], BASE[k]);
             }
         }
       }
@@ -1300,7 +1423,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
     for (int q = 0; q < (int)CH; q++)
       if ((cb >> q) & 1u) CW[q * 64 + lane] = INF64;
     wave_lds_sync();
-    ej = ej2; rj = rj2; cj = cj2; sv = sv2; ro = ro2; dw = dw2;
+    ej = ej2; rj = rj2; cj = cj2; sv = sv2; ro = ro2; dw = dw2; swh = swh2;
     PP_T(tE);
     PP_ADD(6, tE - tD);
   }
