@@ -356,8 +356,7 @@ namespace {
 // Bytes per ncclSend / ncclRecv piece of the record exchange: 2^30 by default
 // (DESIGN.md §5); GS_RCCL_PIECE_BYTES lowers it (tests force many pieces).
 uint64_t rccl_piece_bytes() {  // read per bucket: tests change it between runs
-  const char* e = getenv("GS_RCCL_PIECE_BYTES");
-  const long long x = e && *e ? atoll(e) : 0;
+  const long x = env_int("GS_RCCL_PIECE_BYTES", 0);
   return x > 0 ? std::min<uint64_t>((uint64_t)x, 1ull << 30) : (1ull << 30);
 }
 
@@ -642,12 +641,10 @@ bool run_batch_lp(gs_comm* cm, Ctx** cx, uint32_t nctx, const gs_publish* sched,
   // destination contexts (no copies); ranks gather by default. GS_PART_ROUTE
   // = 1 / 0 forces routed / gathered (loop-back routed then goes through send
   // segments and copies, as ranks do, when GS_PART_DIRECT=0).
-  const char* rte = getenv("GS_PART_ROUTE");
   bool one_dev = cm->local != 0;
   for (uint32_t i = 1; i < nctx; i++) one_dev = one_dev && cx[i]->cfg.device == cx[0]->cfg.device;
-  const char* dre = getenv("GS_PART_DIRECT");
-  const bool direct_ok = one_dev && P <= PART_ROUTE_PMAX && !(dre && *dre && atoi(dre) == 0);
-  const bool routed = P <= PART_ROUTE_PMAX && ((rte && *rte) ? atoi(rte) != 0 : direct_ok);
+  const bool direct_ok = one_dev && P <= PART_ROUTE_PMAX && !env_off("GS_PART_DIRECT");
+  const bool routed = P <= PART_ROUTE_PMAX && env_int("GS_PART_ROUTE", direct_ok) != 0;
   const bool direct = routed && direct_ok;
   for (;;) {
     for (uint32_t i = 0; i < nctx; i++) {

@@ -1,7 +1,6 @@
 // gs_ctx.hip — C-ABI entry points of libgossipsim (include/gossipsim.h):
 // context lifecycle, argument validation, error capture. No exception crosses
 // the ABI; every failure becomes a gs_status plus gs_last_error text.
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -13,23 +12,13 @@ struct gs_ctx : gs::Ctx {};
 namespace gs {
 
 Ctx::~Ctx() {
-  static const bool dbg = getenv("GS_DEBUG_DTOR") != nullptr;
-  auto say = [&](const char* w) {
-    if (dbg) fprintf(stderr, "[dtor] %s\n", w);
-  };
-  say("sync streams");
-  for (hipStream_t st : {side, chain, chain_pipe, pass_ms, copy, stream})
+  for (hipStream_t st : {side, chain_pipe, pass_ms, copy, stream})
     if (st) (void)hipStreamSynchronize(st);
-  say("events");
   for (auto e : ev_pool) (void)hipEventDestroy(e);
   for (auto e : side_ev) (void)hipEventDestroy(e);
   for (auto e : blk_ev)
     if (e) (void)hipEventDestroy(e);
-  say("side");
   if (side) (void)hipStreamDestroy(side);
-  say("chain");
-  if (chain) (void)hipStreamDestroy(chain);
-  say("chain_pipe");
   if (chain_pipe) (void)hipStreamDestroy(chain_pipe);
   for (auto e : chain_ev)
     if (e) (void)hipEventDestroy(e);
@@ -40,7 +29,6 @@ Ctx::~Ctx() {
   }
   for (auto& v : cp_ev)
     for (auto e : v) (void)hipEventDestroy(e);
-  say("pass_ms");
   if (pass_ms) (void)hipStreamDestroy(pass_ms);
   for (auto e : pass_ev)
     if (e) (void)hipEventDestroy(e);
@@ -52,9 +40,7 @@ Ctx::~Ctx() {
   if (h_pinned) (void)hipHostFree(h_pinned);
   if (h_block) (void)hipHostFree(h_block);
   if (h_slms) (void)hipHostFree(h_slms);
-  say("stream");
   if (stream) (void)hipStreamDestroy(stream);
-  say("done");
 }
 
 uint64_t read_counter(Ctx& c, uint32_t idx) {

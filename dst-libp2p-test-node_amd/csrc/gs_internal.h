@@ -2,6 +2,7 @@
 // translation units of libgossipsim (not part of the C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdlib.h>
 
 #include <functional>
 #include <string>
@@ -24,6 +25,20 @@ struct Error {
   std::string msg;
   Error(gs_status c, std::string m) : code(c), msg(std::move(m)) {}
 };
+
+// Environment knobs (DESIGN.md §6.1 lists every one the library reads). Both
+// call getenv every time: tests set os.environ between runs of one process. A
+// knob read once per process is cached by its caller in a static.
+// env_off: set, non-empty and 0 (the switches that are on unless turned off).
+inline bool env_off(const char* name) {
+  const char* e = getenv(name);
+  return e && *e && atoi(e) == 0;
+}
+// env_int: the value, or dflt when unset or empty.
+inline long env_int(const char* name, long dflt) {
+  const char* e = getenv(name);
+  return e && *e ? atol(e) : dflt;
+}
 
 // Device-side error word bits (set by kernels, checked by the host).
 // ERR_LIST: a list pull candidate list overflowed; ERR_RING: a list pull candidate
@@ -81,12 +96,9 @@ struct Ctx {
   std::string last_error;
   hipStream_t stream = nullptr;
   hipStream_t side = nullptr;           // second stream: churn IHAVE lists beside the epoch steps
-  // churn: the epoch chain's own stream, restricted to GS_CHAIN_CUS compute units
-  // (hipExtStreamCreateWithCUMask), and its join events
-  hipStream_t chain = nullptr;
-  hipEvent_t chain_ev[2] = {nullptr, nullptr};
-  hipStream_t chain_pipe = nullptr;  // churn runs: the chain's stream on its own XCD (GS_CHAIN_XCDS, default 0)
   std::vector<hipEvent_t> side_ev;      // its chunk events
+  hipStream_t chain_pipe = nullptr;  // churn runs: the chain's stream on its own XCD (GS_CHAIN_XCDS, default 0)
+  hipEvent_t chain_ev[2] = {nullptr, nullptr};  // its join events with the context's stream (churn_ring)
   bool timing = false;
   bool traffic = false;        // gs_set_traffic: per-peer send/receive counters
   DevBuf<uint64_t> d_traffic;  // [N][GS_TRAFFIC_COLS]
@@ -310,7 +322,6 @@ struct Ctx {
   gs_stats stats{};
   std::vector<hipEvent_t> ev_pool;
   int num_cus = 0;
-  uint32_t split_bpc = 0;  // blocks per CU of the split path's grid (split_blocks_per_cu)
   std::string gossip_why;  // the message that broke the last partitioned gossip no-op proof
 
   ~Ctx();
@@ -326,8 +337,6 @@ inline void ensure_cus(Ctx& c) {
     c.num_cus = hipGetDeviceProperties(&prop, c.cfg.device) == hipSuccess ? prop.multiProcessorCount : 256;
   }
 }
-hipStream_t cu_stream(Ctx& c, uint32_t c0, uint32_t n);
-hipStream_t cu_stream_except(Ctx& c, uint32_t c0, uint32_t stride);
 hipStream_t xcd_stream(Ctx& c, uint32_t xcds);
 uint32_t xcd_env(const char* name);
 void churn_ring(Ctx& c, uint64_t h_lo, uint64_t h_hi);

@@ -479,27 +479,10 @@ __device__ __forceinline__ void glp_ihave_ent(const LPullArgs& a, uint64_t* CW, 
 // Record step: NG = 4 neighbours, RCH = 2 chunks of 64 records each (8 loads in
 // flight per lane; 8 x 64 measured 2 % slower,
 // profiles/r03_v1/ab_record_groups.txt), as NG streams of RCH register slots
-// on single-fragment rows (GS_LP_STREAM) and as groups loaded,
-// awaited and processed together elsewhere. GS_LP_NG / GS_LP_RCH: A/B builds
-// of either form.
-#ifndef GS_LP_NG
-#define GS_LP_NG 4
-#endif
-#ifndef GS_LP_NT  // nontemporal stores of the final log (A/B: -DGS_LP_NT=0)
-#define GS_LP_NT 1
-#endif
-#ifndef GS_LP_NTR  // nontemporal stores of the records (A/B variant; off)
-#define GS_LP_NTR 0
-#endif
-#ifndef GS_LP_RCH
-#define GS_LP_RCH 2
-#endif
-#ifndef GS_LP_STREAM  // the non-churn record step as streams (1) or as load-all, wait-all, process-all groups (0)
-#define GS_LP_STREAM 1
-#endif
-#ifndef GS_LP_SKIP  // (groups only) record chunks past a neighbour's count skipped by a scalar branch (off: +1.3 % per step, r06)
-#define GS_LP_SKIP 0
-#endif
+// on single-fragment rows (STREAM) and as groups loaded,
+// awaited and processed together elsewhere. The final log is stored
+// non-temporally and the records plainly; a scalar branch that skipped record
+// chunks past a neighbour's count cost 1.3 % per step (DESIGN.md Round 6 log).
 // NOLOG (the trailing parameter: profilers match the name by its leading FP, CH):
 // a batch of which the caller reads only counters. The
 // emit step writes no final log; each final adds its latency in ms and its key
@@ -511,10 +494,10 @@ __device__ __forceinline__ void glp_ihave_ent(const LPullArgs& a, uint64_t* CW, 
 template <int FP, uint32_t CH, bool IDW = false, bool PART = false, bool GOS = false, bool CHN = false,
           bool NOLOG = false>
 __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
-  constexpr uint32_t NG = GS_LP_NG, RCH = GS_LP_RCH;
+  constexpr uint32_t NG = 4, RCH = 2;
   // (fragment groups keep the grouped record step: they sit at their VGPR limit, and the
   // streamed form's two per-lane table values cost every FP > 1 instantiation scratch)
-  constexpr bool STREAM = GS_LP_STREAM != 0 && FP == 1;
+  constexpr bool STREAM = FP == 1;
   static_assert(!NOLOG || (FP == 1 && !IDW && !PART && !GOS && !CHN),
                 "no final log: rows of single-fragment lanes on gs_run's frozen mesh, eager forwarding only");
   static_assert(!GOS || !PART, "gossip on the list pass: gs_run's rows");
@@ -969,7 +952,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
       const uint64_t lo = wlo - a.delta;  // the window whose records are pulled
       uint64_t cmk = cand;
       if constexpr (STREAM) {
-        // Streamed form (GS_LP_STREAM): NG neighbour contexts in scalar
+        // Streamed form (single-fragment rows): NG neighbour contexts in scalar
         // registers, each streaming its neighbour's 64-record chunks through
         // its own RCH register slots. A context's turn processes its slots,
         // steps to the neighbour's next chunks or, when none is left, takes the
@@ -1108,10 +1091,6 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
               // neighbour's NN records it reads 0, which no record is (a
               // forwarding sender has hops >= 1)
               const uint32_t i = i0 + cc * 64 + lane;
-              if (GS_LP_SKIP && i0 + cc * 64 >= NN[k]) {  // wave-uniform: a chunk past every record
-                rec[k][cc] = 0;
-                continue;
-              }
               const auto v = __builtin_amdgcn_raw_buffer_load_b64(RS[k], i * 8u, 0, 0);
               rec[k][cc] = ((uint64_t)v[1] << 32) | v[0];
             }
@@ -1122,10 +1101,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
 #pragma unroll
           for (int k = 0; k < (int)NG; k++)
 #pragma unroll
-            for (int cc = 0; cc < (int)RCH; cc++) {
-              if (GS_LP_SKIP && i0 + cc * 64 >= NN[k]) continue;  // (nothing loaded: no record)
-              relax_rec(rec[k][cc], IB[k], LB[k], SER[k], BASE[k]);
-            }
+            for (int cc = 0; cc < (int)RCH; cc++) relax_rec(rec[k][cc], IB[k], LB[k], SER[k], BASE[k]);
         }
       }
     }
@@ -1362,13 +1338,9 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
           if (act) {
             const uint32_t p =
                 logc + __builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
-            if (GS_LP_NT) {  // the final log is read after the passes (completion): stream it past the caches
-              __builtin_nontemporal_store(x, &a.keys[(size_t)w * LL + p]);
-              __builtin_nontemporal_store((uint16_t)i, &a.flane[(size_t)w * LL + p]);
-            } else {
-              a.keys[(size_t)w * LL + p] = x;
-              a.flane[(size_t)w * LL + p] = (uint16_t)i;
-            }
+            // the final log is read after the passes (completion): stream it past the caches
+            __builtin_nontemporal_store(x, &a.keys[(size_t)w * LL + p]);
+            __builtin_nontemporal_store((uint16_t)i, &a.flane[(size_t)w * LL + p]);
           }
           logc += (uint32_t)__popcll(fm);
         }
@@ -1384,8 +1356,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
                 make_uint4((uint32_t)r0, (uint32_t)(r0 >> 32), (uint32_t)im64, (uint32_t)(im64 >> 32));
           } else {
             const uint64_t rv = ((start - wlo) << 32) | ((uint64_t)hp << LP_HOP_SHIFT) | ((uint64_t)im << LP_IM_SHIFT) | i;
-            if (GS_LP_NTR) __builtin_nontemporal_store(rv, &wrec[ri]);
-            else wrec[ri] = rv;
+            wrec[ri] = rv;
           }
         }
         ecnt += (uint32_t)__popcll(wm);
@@ -2104,11 +2075,8 @@ __global__ __launch_bounds__(TB) void k_lsum(LPullArgs a, uint64_t* bw) {
 }
 
 // Chunks per row of the pass: 8 when a row has <= 512 lanes (half the LDS,
-// twice the resident waves), else 16. GS_LPULL_CH=16 forces the wide form.
-uint32_t lpull_chunks(uint32_t L) {
-  const char* e = getenv("GS_LPULL_CH");  // per launch: A/B scripts switch it in one process
-  return (L <= 512 && !(e && atoi(e) == 16)) ? 8u : 16u;
-}
+// twice the resident waves), else 16.
+uint32_t lpull_chunks(uint32_t L) { return L <= 512 ? 8u : 16u; }
 
 // Partitioned pass: this part's records of the pass (lrec[nb] / lcnt[nb], by
 // local row) packed straight into its own range of the next pass's packed

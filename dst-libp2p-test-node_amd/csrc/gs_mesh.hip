@@ -39,7 +39,7 @@ struct MeshArgs {
   uint64_t seed;
   uint32_t N, S, epoch, bo, d, d_lo, d_hi, d_out;
   uint32_t sub;  // the subscription epoch 0: handshake-ordered grafts; = handshake RTTs (0: a heartbeat)
-  // event-driven churn epochs (run_epochs): per-peer state planes, nullptr when
+  // event-driven churn epochs (ev_epochs): per-peer state planes, nullptr when
   // every row runs every step
   uint8_t* pst;              // [PS_PLANES][N]
   const uint64_t* off_prev;  // offline bitsets of the previous and the next epoch
@@ -740,7 +740,7 @@ __global__ __launch_bounds__(TB) void k_csrpos(uint32_t N, const uint64_t* __res
   }
 }
 
-// ---- event-driven churn epochs (the default run_epochs path) ----
+// ---- event-driven churn epochs (ev_epochs) ----
 // Under churn most rows do nothing in a given epoch (1 % departures per epoch:
 // ~18 % of the rows change, most of them by one dropped link). Each step of an
 // epoch therefore tests a few per-peer flags (MeshArgs::pst) and runs the
@@ -926,8 +926,9 @@ __device__ __forceinline__ void row_apply_ev(const MeshArgs& a, uint32_t u, uint
 // can change into LDS; then every group of G lanes takes active rows (most
 // blocks have a handful, so one round). Steps:
 enum : int { EV_HB = 0, EV_GRAFT = 1, EV_APPLY = 2 };
-// SW scanning waves per block: a block owns 64 * SW rows (GS_EV_SW; the steps
-// are short, so the number of workgroups per launch matters, not only the rows)
+// SW scanning waves per block: a block owns 64 * SW rows (ev_epoch launches
+// SW = 1: the steps are short, so the number of workgroups per launch matters,
+// not only the rows; 2 and 4 measured slower, DESIGN.md Round 6 log)
 template <int G, int STEP, int SW>
 __global__ __launch_bounds__(TB) void k_ev_step(MeshArgs a, uint32_t* mesh, const uint32_t* mesh_prev) {
   constexpr uint32_t RW = 64u * SW;
@@ -1042,12 +1043,8 @@ __global__ __launch_bounds__(TB) void k_ev_step(MeshArgs a, uint32_t* mesh, cons
 inline unsigned blocks(uint64_t n) { return (unsigned)((n + TB - 1) / TB); }
 
 // Lanes per peer of the row kernels: 16 (four peers per wave) when every row
-// fits 4 x 16 entries, else 64 (GS_ROW_GROUP=64 forces one peer per wave).
-inline uint32_t row_group(const Ctx& c) {
-  static const char* e = getenv("GS_ROW_GROUP");
-  if (e && atoi(e) == 64) return 64u;
-  return c.max_degree <= 4 * 16 ? 16u : 64u;
-}
+// fits 4 x 16 entries, else 64.
+inline uint32_t row_group(const Ctx& c) { return c.max_degree <= 4 * 16 ? 16u : 64u; }
 inline unsigned row_blocks(uint32_t N, uint32_t G) { return (unsigned)(((uint64_t)N * G + TB - 1) / TB); }
 #define GS_ROWS(kernel, G, N, s, ...)                                                   \
   do {                                                                                   \
@@ -1100,10 +1097,7 @@ static hipEvent_t side_event(Ctx& c, size_t i) {
   if (!c.side) {  // lowest priority: the epoch steps' dependent chain is dispatched first
     int lo = 0, hi = 0;
     GS_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    const char* sp = getenv("GS_SIDE_PRIORITY");  // A/B knob: 0 = default priority
-    if (const uint32_t x = xcd_env("GS_SIDE_XCDS")) c.side = xcd_stream(c, x);  // (experiment: its XCDs)
-    else if (sp && *sp && atoi(sp) == 0) GS_HIP(hipStreamCreateWithFlags(&c.side, hipStreamNonBlocking));
-    else GS_HIP(hipStreamCreateWithPriority(&c.side, hipStreamNonBlocking, lo));
+    GS_HIP(hipStreamCreateWithPriority(&c.side, hipStreamNonBlocking, lo));
   }
   while (c.side_ev.size() <= i) {
     hipEvent_t e;
@@ -1157,22 +1151,11 @@ void sub_epoch(Ctx& c, MeshArgs a) {
 static void ev_epoch(Ctx& c, MeshArgs& a, uint64_t h, uint64_t h0, uint64_t h1, const uint64_t* lin, uint32_t w64,
                      bool ring, bool ell, uint32_t G, hipStream_t s) {
   const uint32_t N = c.cfg.peers;
-  static const uint32_t ev_sw = [] {  // GS_EV_SW: scanning waves (rows / 64) per block of the steps
-    const char* e = getenv("GS_EV_SW");
-    const int v = e && *e ? atoi(e) : 1;
-    return (uint32_t)(v >= 4 ? 4 : v >= 2 ? 2 : 1);
-  }();
-  const unsigned sgrid = (unsigned)((N + 64 * ev_sw - 1) / (64 * ev_sw));
-#define GS_EVS1(SW, STEP, ...)                                                     \
-  do {                                                                             \
-    if (G == 16) k_ev_step<16, STEP, SW><<<sgrid, TB, 0, s>>>(__VA_ARGS__);        \
-    else k_ev_step<64, STEP, SW><<<sgrid, TB, 0, s>>>(__VA_ARGS__);                \
-  } while (0)
+  const unsigned sgrid = (unsigned)((N + 63) / 64);  // one scanning wave (64 rows) per block of the steps
 #define GS_EVS(STEP, ...)                                                          \
   do {                                                                             \
-    if (ev_sw == 4) GS_EVS1(4, STEP, __VA_ARGS__);                                 \
-    else if (ev_sw == 2) GS_EVS1(2, STEP, __VA_ARGS__);                            \
-    else GS_EVS1(1, STEP, __VA_ARGS__);                                            \
+    if (G == 16) k_ev_step<16, STEP, 1><<<sgrid, TB, 0, s>>>(__VA_ARGS__);         \
+    else k_ev_step<64, STEP, 1><<<sgrid, TB, 0, s>>>(__VA_ARGS__);                 \
   } while (0)
   const uint64_t y = h - h0 + 1;
   a.epoch = (uint32_t)h;
@@ -1195,7 +1178,6 @@ static void ev_epoch(Ctx& c, MeshArgs& a, uint64_t h, uint64_t h0, uint64_t h1, 
   GS_EVS(EV_GRAFT, an, nullptr, nullptr);
   GS_EVS(EV_APPLY, a, mesh, prev);
 #undef GS_EVS
-#undef GS_EVS1
 }
 
 // Event-driven churn epochs [h0, h1] (see k_ev_step): offline bitsets
@@ -1248,8 +1230,7 @@ void ev_epochs(Ctx& c, MeshArgs a, uint64_t h0, uint64_t h1, bool ring) {
   // chunk as soon as its epochs are stepped (compute-bound list kernels beside
   // the latency-bound epoch steps)
   const bool lists = ring && ring_in_wanted(c);
-  const char* sb = getenv("GS_SIDE_BPC");  // list blocks per CU beside the steps (0: full grid)
-  const uint32_t side_bpc = sb && *sb ? (uint32_t)atoi(sb) : 2u;
+  const uint32_t side_bpc = 2;  // list blocks per CU beside the steps (0: full grid)
   const uint64_t CE = ring_in_chunk_epochs(N);
   uint64_t chunk0 = hr;
   size_t nev = 0;
@@ -1286,10 +1267,6 @@ void ev_epochs(Ctx& c, MeshArgs a, uint64_t h0, uint64_t h1, bool ring) {
   }
 }
 
-// Churn epochs [h0, h1] from the current mesh state (ev_epochs); `ring`:
-// also the ELL snapshots (+ inverse IHAVE lists) into the ring slots h % ring_R.
-void run_epochs(Ctx& c, MeshArgs a, uint64_t h0, uint64_t h1, bool ring) { ev_epochs(c, a, h0, h1, ring); }
-
 }  // namespace
 
 hipStream_t side_stream(Ctx& c) {
@@ -1315,40 +1292,6 @@ void ensure_in_lists(Ctx& c, uint64_t h0, uint64_t h1) {
     h = e + 1;
   }
   GS_HIP(hipGetLastError());
-}
-
-// Make the churn ring hold the snapshots of epochs [h_lo, h_hi] (h_hi - h_lo
-// < ring_R): replay from the empty mesh when h_lo has left the ring, else run
-// the epochs after the current mesh state. Snapshot h = mesh after heartbeat h
-// with the offline bits of epoch h; epoch 0 is the empty mesh, all online.
-// A stream restricted to n compute units (bits [c0, c0 + n) of
-// hipExtStreamCreateWithCUMask's mask; GS_CU_STRIDE=s takes every s-th bit).
-hipStream_t cu_stream(Ctx& c, uint32_t c0, uint32_t n) {
-  ensure_cus(c);
-  const uint32_t total = (uint32_t)std::max(c.num_cus, 1);
-  const char* st = getenv("GS_CU_STRIDE");
-  const uint32_t stride = st && *st ? (uint32_t)std::max(1, atoi(st)) : 1u;
-  std::vector<uint32_t> mask((total + 31) / 32, 0u);
-  for (uint32_t i = 0; i < n; i++) {
-    const uint32_t b = (c0 + i * stride) % total;
-    mask[b / 32] |= 1u << (b % 32);
-  }
-  hipStream_t s = nullptr;
-  GS_HIP(hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()));
-  return s;
-}
-
-// A stream on every CU except the bits c0, c0 + stride, ... (the complement of
-// cu_stream(c, c0, total / stride) with GS_CU_STRIDE = stride).
-hipStream_t cu_stream_except(Ctx& c, uint32_t c0, uint32_t stride) {
-  ensure_cus(c);
-  const uint32_t total = (uint32_t)std::max(c.num_cus, 1);
-  std::vector<uint32_t> mask((total + 31) / 32, 0u);
-  for (uint32_t b = 0; b < total; b++)
-    if (stride == 0 || b < c0 || (b - c0) % stride != 0) mask[b / 32] |= 1u << (b % 32);
-  hipStream_t s = nullptr;
-  GS_HIP(hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()));
-  return s;
 }
 
 // A stream on the CUs of the XCDs in `xcds` (bit x: XCD x). The CU mask's bit b
@@ -1386,27 +1329,16 @@ uint32_t xcd_env(const char* name) {
   return m;
 }
 
-// GS_CHAIN_CUS=n (experiment): the epoch chain of churn_ring on a stream of n CUs.
-static uint32_t chain_cus() {
-  const char* e = getenv("GS_CHAIN_CUS");
-  if (const uint32_t x = xcd_env("GS_CHAIN_XCDS")) return 0x10000u | x;  // (GS_CHAIN_XCDS wins)
-  return e && *e ? (uint32_t)std::max(0, atoi(e)) : 0u;
-}
-
+// Make the churn ring hold the snapshots of epochs [h_lo, h_hi] (h_hi - h_lo
+// < ring_R): replay from the empty mesh when h_lo has left the ring, else run
+// the epochs after the current mesh state. Snapshot h = mesh after heartbeat h
+// with the offline bits of epoch h; epoch 0 is the empty mesh, all online.
+// The chain runs on c.chain_pipe (its own XCD, gs_relax.hip PassStream) when
+// the run made one, else on the context's stream.
 static void churn_ring_on(Ctx& c, uint64_t h_lo, uint64_t h_hi);
 void churn_ring(Ctx& c, uint64_t h_lo, uint64_t h_hi) {
-  const uint32_t n = c.chain_pipe ? 0u : chain_cus();
-  if (!n && !c.chain_pipe) return churn_ring_on(c, h_lo, h_hi);
-  static uint32_t made = 0;  // (experiment: one mask per process)
-  if (!c.chain_pipe && (!c.chain || made != n)) {
-    if (c.chain) GS_HIP(hipStreamDestroy(c.chain));
-    c.chain = n & 0x10000u ? xcd_stream(c, n & 0xFFu) : cu_stream(c, 0, n);
-    made = n;
-    for (auto& e : c.chain_ev)
-      if (e) GS_HIP(hipEventDestroy(e));
-    for (auto& e : c.chain_ev) GS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  hipStream_t main = c.stream, cs = c.chain_pipe ? c.chain_pipe : c.chain;
+  if (!c.chain_pipe) return churn_ring_on(c, h_lo, h_hi);
+  hipStream_t main = c.stream, cs = c.chain_pipe;
   for (auto& e : c.chain_ev)
     if (!e) GS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   GS_HIP(hipEventRecord(c.chain_ev[0], main));
@@ -1448,7 +1380,7 @@ static void churn_ring_on(Ctx& c, uint64_t h_lo, uint64_t h_hi) {
     }
   }
   if (c.churn_state + 1 <= h_hi)
-    run_epochs(c, a, c.churn_state + 1, h_hi, true);
+    ev_epochs(c, a, c.churn_state + 1, h_hi, true);
   GS_HIP(hipGetLastError());
   if (h_hi > c.churn_state) {
     c.churn_state = h_hi;
@@ -1589,7 +1521,7 @@ uint32_t run_mesh(Ctx& c, uint32_t max_hb) {
   uint32_t epoch = 1, last = 0;
   uint64_t* h = c.h_pinned;
   if (c.cfg.churn_ppm) {  // no fixed point under churn: exactly max_hb epochs
-    if (max_hb >= 1) run_epochs(c, a, 1, max_hb, false);
+    if (max_hb >= 1) ev_epochs(c, a, 1, max_hb, false);
     last = max_hb;
     c.churn_state = max_hb;  // the ring restarts after this state
     c.ring_lo = (uint64_t)max_hb + 1;

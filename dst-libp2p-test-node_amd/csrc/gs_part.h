@@ -399,7 +399,7 @@ uint64_t part_begin(Ctx& c, const gs_publish* sched, uint64_t n_msgs) {
   GS_HIP(hipMemsetAsync(c.d_fbits.p, 0, (total + 63) / 64 * 8, s));
   GS_HIP(hipMemsetAsync(c.d_ctrl.p, 0xFF, 4 * 8, s));
   c.part_grid = (unsigned)std::max<uint64_t>(
-      1, std::min<uint64_t>((total + TB - 1) / TB, (uint64_t)c.num_cus * split_blocks_per_cu(c)));
+      1, std::min<uint64_t>((total + TB - 1) / TB, (uint64_t)c.num_cus * SPLIT_BLOCKS_PER_CU));
   const uint64_t nwaves = (uint64_t)c.part_grid * (TB / 64), ntiles = (total + 63) / 64;
   c.part_seg_cap = (uint32_t)(((ntiles + nwaves - 1) / nwaves) * (64 / FP));
   c.d_fr_idx.alloc(nwaves * c.part_seg_cap);
@@ -672,8 +672,7 @@ static LPullArgs part_lp_args(Ctx& c) {
   la.N = un; la.B = b.B; la.L = L; la.S = c.S; la.sb = b.sb; la.tshift = b.tshift;
   la.K = c.part_lpK; la.lb = c.part_lplb; la.dG = (uint32_t)(la.delta / grain);
   la.ls = lpull_stride(b);
-  const char* cap = getenv("GS_LPULL_CAP");
-  la.lcap = cap && *cap ? (uint32_t)std::min<long>(std::max(1, atoi(cap)), (long)la.ls) : la.ls;
+  la.lcap = (uint32_t)std::min<long>(std::max(1l, env_int("GS_LPULL_CAP", (long)la.ls)), (long)la.ls);
   la.u0 = c.part_u0;
   la.rmax = lpull_rmax(b);
   la.rpk = c.d_rpk.p; la.roff = c.d_roffg.p; la.rcg = c.d_rcg.p;
@@ -684,8 +683,8 @@ static LPullArgs part_lp_args(Ctx& c) {
 bool part_lp_begin(Ctx& c, const gs_publish* sched, uint64_t n_msgs) {
   const uint32_t F = part_check(c, sched, n_msgs);
   (void)F;
-  const char* ve = getenv("GS_RELAX_VARIANT");  // without bit 64 (or GS_PART_PUSH) the push protocol runs
-  if ((ve && *ve && !(atoi(ve) & 64)) || getenv("GS_PART_PUSH")) return false;
+  // without bit 64 (or with GS_PART_PUSH) the push protocol runs
+  if (!(env_int("GS_RELAX_VARIANT", 64) & 64) || getenv("GS_PART_PUSH")) return false;
   hipStream_t s = c.stream;
   GS_HIP(hipMemsetAsync(c.d_counters.p + C_ERR, 0, 8, s));
   ensure_cus(c);

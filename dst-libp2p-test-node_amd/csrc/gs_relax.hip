@@ -878,8 +878,7 @@ static RelaxArgs relax_args(Ctx& c, const Batch& b, bool gossip) {
       ra.ring_in = c.d_ring_in.p;
       // heartbeats of a message from index gs_switch on are decided
       // sender-centric (exact for any value; GS_GOSSIP_SWITCH for tests / A/B)
-      const char* gsw = getenv("GS_GOSSIP_SWITCH");
-      ra.gs_switch = gsw && *gsw ? (uint32_t)atoi(gsw) : 4u;
+      ra.gs_switch = (uint32_t)env_int("GS_GOSSIP_SWITCH", 4);
       // the per-lane first gossip heartbeat (RelaxArgs::hwin) saturates at 254:
       // the receiver-centric test k < j0 needs gs_switch <= 254 to stay exact
       // (a larger switch puts every heartbeat of a 16-epoch lifetime on that side anyway)
@@ -1060,8 +1059,8 @@ static uint32_t lpull_ring(Ctx& c, const Batch& b, uint64_t delta, uint32_t* lb,
   if (gos) K = std::max<uint64_t>(K, (delta + b.ans_max) / delta + 2);
   if (K > LP_KMAX) return 0;
   // test knob: a ring smaller than the bound forces ERR_RING and the k_pull re-run
-  const char* kf = getenv("GS_LPULL_K");  // per batch: tests set it between runs
-  if (kf && *kf) K = std::min<uint64_t>(K, (uint64_t)std::max(2, atoi(kf)));
+  // (per batch: tests set it between runs)
+  K = std::min<uint64_t>(K, (uint64_t)std::max(2l, env_int("GS_LPULL_K", LP_KMAX)));
   uint32_t tb = 0;
   while ((1ull << tb) < delta) tb++;
   *lb = bits_for(b.L);
@@ -1226,15 +1225,14 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
     // them (GS_GOSSIP_SWITCH, any value is exact). Off by default: at config #3's
     // shape the pushes cost more in k_gsend than the plane scans they replace
     // (121 ms per batch without, 129 ms from heartbeat 4 on, 193 ms from 1 on)
-    const char* gsw = getenv("GS_GOSSIP_SWITCH");
-    la.gsw = gsw && *gsw ? (uint32_t)atoi(gsw) : ~0u;
+    la.gsw = (uint32_t)env_int("GS_GOSSIP_SWITCH", ~0u);
   }
   // test knobs, read per batch: GS_LPULL_CAP's small lists force the overflow re-run;
   // GS_LPULL_CAP_BATCHES (comma-separated 0-based indices of the run's batch loop, in run
   // order: after the class regrouping) keeps the cap to the listed batches
-  const char* cap = getenv("GS_LPULL_CAP");
+  long cap = env_int("GS_LPULL_CAP", (long)ls);
   const char* capb = getenv("GS_LPULL_CAP_BATCHES");
-  if (cap && capb && *capb) {
+  if (capb && *capb) {
     bool listed = false;
     for (const char* q = capb; *q && !listed;) {
       char* end = nullptr;
@@ -1243,31 +1241,26 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
       q = end != q ? end : q + 1;
       while (*q == ',' || *q == ' ') q++;
     }
-    if (!listed) cap = nullptr;
+    if (!listed) cap = (long)ls;
   }
   la.ls = ls;
-  la.lcap = cap && *cap ? (uint32_t)std::min<long>(std::max(1, atoi(cap)), (long)ls) : ls;
+  la.lcap = (uint32_t)std::min<long>(std::max(1l, cap), (long)ls);
   // 40 KB of LDS per block: 4 blocks (16 waves, 16 rows in flight) resident per
   // CU. Large graphs launch up to 16 blocks per CU so that a pass's tail is
   // made of short blocks, keeping >= 32 rows per wave (1M peers: 54.3 ms per
   // step at 4 blocks per CU, 53.1 at 16; 100k peers: 7.8 ms at 16, 6.8 at 4;
-  // profiles/r02_v7/lpull_grid_sweep.txt); GS_LPULL_BPC fixes blocks per CU
-  const uint64_t bpc = [] {  // per batch: A/B scripts switch it in one process
-    const char* e = getenv("GS_LPULL_BPC");
-    return (uint64_t)(e && *e ? std::max(1, atoi(e)) : 0);
-  }();
+  // profiles/r02_v7/lpull_grid_sweep.txt)
   // a power of two: 15 per CU measured 56.4 ms against 53.1 at 16 on one box
   uint64_t auto_bpc = 4;
   while (auto_bpc < 16 && (uint64_t)N >= (uint64_t)dev_cus * PULL_WAVES * 32 * auto_bpc * 2) auto_bpc *= 2;
-  const uint64_t want = (uint64_t)dev_cus * (bpc ? bpc : auto_bpc);  // whole blocks per CU
+  const uint64_t want = (uint64_t)dev_cus * auto_bpc;  // whole blocks per CU
   unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)N + PULL_WAVES - 1) / PULL_WAVES, want));
   k_lseed<<<(unsigned)std::max<uint64_t>(1, std::min<uint64_t>((scap + TB - 1) / TB, (uint64_t)dev_cus * 4)), TB, 0, s>>>(
       la, c.d_skey.p, c.d_slane.p, c.d_scnt.p);
-  {  // the rows whose emit step needs the publishers (LP_PUB); GS_LPULL_PUBW=0: every row loads them
-    const char* pw = getenv("GS_LPULL_PUBW");  // per batch: A/B scripts switch it in one process
-    la.pubw = pw && *pw && atoi(pw) == 0 ? 0u : 1u;
+  {  // the rows whose emit step needs the publishers (LP_PUB)
+    la.pubw = 1;
     const uint64_t nm = (uint64_t)(sl ? sl->S : 1u) * b.B, width = (chn ? CELL_W : MESH_W) + 1;
-    if (la.pubw) k_lpubnb<<<(unsigned)((nm * width + TB - 1) / TB), TB, 0, s>>>(la, (uint32_t)nm);
+    k_lpubnb<<<(unsigned)((nm * width + TB - 1) / TB), TB, 0, s>>>(la, (uint32_t)nm);
   }
   for (uint32_t j = 0; j < (sl ? sl->S : 1u); j++) {  // (a slice's publishers are its rows)
     LPullArgs lj = la;
@@ -1389,14 +1382,7 @@ extern "C" int gs_debug_pull_prof(uint64_t* out) {  // 32 passes x 8 slots; read
 // Blocks per CU of the split (push) path's scan / frontier / gossip grid: 4
 // measured best on config #3 (k_scan 177 -> 136 us, k_frontier 65 -> 38 us per
 // bucket vs 16; 1-2 and 32-64 slower, profiles/r01_v10/c3_grid_sweep.txt).
-// GS_SPLIT_BLOCKS_PER_CU overrides it (read once per context).
-static uint32_t split_blocks_per_cu(Ctx& c) {
-  if (!c.split_bpc) {
-    const char* e = getenv("GS_SPLIT_BLOCKS_PER_CU");
-    c.split_bpc = e && *e ? (uint32_t)std::max(1, atoi(e)) : 4u;
-  }
-  return c.split_bpc;
-}
+constexpr uint32_t SPLIT_BLOCKS_PER_CU = 4;
 
 // Lazy gossip is a no-op for message q when every non-publisher completed and
 // the last completion lies before the first IHAVE can arrive: the earliest
@@ -1571,8 +1557,8 @@ static void ensure_ring(Ctx& c) {
   const uint64_t w64 = ((uint64_t)N + 63) / 64;
   const uint64_t per_slot = (uint64_t)N * MESH_W * 4 + w64 * 8 + (gossip ? (uint64_t)N * (GT_IN * 4 + 4) : 0) +
                             (uint64_t)N * 8;
-  const char* rb = getenv("GS_RING_BUDGET_MB");  // test knob: force batch cuts at the ring size
-  const uint64_t budget = rb && *rb ? (uint64_t)atoll(rb) << 20 : 16ull << 30;
+  // test knob: a small budget forces batch cuts at the ring size
+  const uint64_t budget = (uint64_t)env_int("GS_RING_BUDGET_MB", 16 << 10) << 20;
   const uint64_t want = (uint64_t)Bmax + c.cfg.churn_horizon + 1;
   c.ring_R = (uint32_t)std::min<uint64_t>(want, std::max<uint64_t>(c.cfg.churn_horizon + 2, budget / per_slot));
   c.d_ring_mesh.alloc((size_t)c.ring_R * N * MESH_W);
@@ -1594,7 +1580,7 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
 // messages a batch could hold (same size and chunk count, <= the batch size,
 // churn: its epochs in the ring) in offset-class order — a batch per class,
 // each lockstep — and hands the results back in schedule order. Classes per
-// group are capped (GS_CLASS_MAX, default 64; a group with more keeps its
+// group are capped (at 64; a group with more keeps its
 // order); streaming sinks (on_block, on_lat) and device sinks keep the order
 // too. GS_CLASS_SPLIT=0 turns the regrouping off.
 static bool class_plan(Ctx& c, const gs_publish* sched, uint64_t n, const gs_result_sink* sink,
@@ -1602,10 +1588,8 @@ static bool class_plan(Ctx& c, const gs_publish* sched, uint64_t n, const gs_res
   const bool churn = c.cfg.churn_ppm != 0, gossip = c.cfg.lazy_gossip != 0;
   if ((!churn && !gossip) || n < 2 || c.sink_dev) return false;
   if (sink && (sink->on_block || sink->on_lat)) return false;
-  const char* e = getenv("GS_CLASS_SPLIT");
-  if (e && *e && atoi(e) == 0) return false;
-  const char* mx = getenv("GS_CLASS_MAX");
-  const uint64_t cmax = mx && *mx ? (uint64_t)std::max(1, atoi(mx)) : 64u;
+  if (env_off("GS_CLASS_SPLIT")) return false;
+  constexpr uint64_t cmax = 64;
   const uint64_t hb = c.cfg.heartbeat_ns, ph = c.cfg.hb_phase_ns;
   for (uint64_t i = 0; i < n; i++)
     if (sched[i].t_pub_ns < ph) return false;  // (run_messages_impl reports what it must)
@@ -1705,16 +1689,14 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
   // chain gets its own XCD (c.chain_pipe, GS_CHAIN_XCDS, default XCD 0) and the
   // rest of the run the others (c.pass_ms, GS_PASS_XCDS, default 1-7): the next
   // batch's chain then runs beside this batch's passes (ChnAhead below).
-  // GS_CHN_PIPE=0 keeps one stream; GS_PASS_SKIP / GS_PASS_XCDS alone: experiments.
+  // GS_CHN_PIPE=0 keeps one stream (GS_PASS_XCDS alone then still moves the passes).
   ensure_cus(c);
-  const char* pipe_env = getenv("GS_CHN_PIPE");
-  const bool pipe_on = c.cfg.churn_ppm && !(pipe_env && *pipe_env && atoi(pipe_env) == 0) && c.num_cus == 256 &&
+  const bool pipe_on = c.cfg.churn_ppm && !env_off("GS_CHN_PIPE") && c.num_cus == 256 &&
                        c.cfg.flood_publish && !c.traffic && !c.sink_dev && !getenv("GS_DEBUG_CHN");
   struct PassStream {
     Ctx& c;
     hipStream_t orig = nullptr;
     PassStream(Ctx& cc, bool pipe) : c(cc) {
-      const char* e = getenv("GS_PASS_SKIP");
       uint32_t px = xcd_env("GS_PASS_XCDS");
       if (pipe) {
         if (!c.chain_pipe) {
@@ -1723,9 +1705,9 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
         }
         if (!px) px = 0xFEu & ~xcd_env("GS_CHAIN_XCDS");
       }
-      if (!px && (!e || !*e || atoi(e) <= 0)) return;
+      if (!px) return;
       if (!c.pass_ms) {  // created once per context (a CU-masked stream costs ~10 ms)
-        c.pass_ms = px ? xcd_stream(c, px) : cu_stream_except(c, 0, (uint32_t)atoi(e));
+        c.pass_ms = xcd_stream(c, px);
         for (auto& ev : c.pass_ev) GS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
       }
       orig = c.stream;
@@ -1747,12 +1729,12 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
   uint32_t Fmax = 1;
   for (uint64_t i = 0; i < n_msgs; i++) Fmax = std::max(Fmax, frags_of(c, sched[i]));
   const uint32_t FPmax = pow2_at_least(Fmax);
-  const char* var_env = getenv("GS_RELAX_VARIANT");
+  const long var_env = env_int("GS_RELAX_VARIANT", -1);  // a bit mask; unset (< 0): the default below
   // default: owner-computes pull over candidate lists (64 | 32), fragmented batches
   // too (128; config #2 7.2e8 against 6.7e8/s on k_pull's dense rows, round 4);
   // k_pull's dense rows without 64; without 32 the push path: split (8) + final
   // bitset (4) + read filter (1)
-  uint32_t variant = var_env && *var_env ? (uint32_t)atoi(var_env) : 237u;
+  uint32_t variant = var_env < 0 ? 237u : (uint32_t)var_env;
   const bool lanes32 = (uint64_t)N * Bmax * FPmax < (1ull << 32);  // frontier indices are u32
   if (!lanes32) variant &= ~8u;
   const bool gossip = c.cfg.lazy_gossip != 0;
@@ -1766,13 +1748,12 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
   // churn on the list pass (gs_cpull.h): lockstep batches (rows of fragment groups
   // included) without IDONTWANT, CSR rows of <= 64 entries (<= 58 with lazy gossip: the IHAVE entry's
   // target mask); GS_CHURN_LIST=0 keeps them on the push path
-  const char* chl_env = getenv("GS_CHURN_LIST");
-  const bool chn_any = churn && (variant & 32) && (variant & 64) && !(chl_env && *chl_env && atoi(chl_env) == 0) &&
+  const bool chn_any = churn && (variant & 32) && (variant & 64) && !env_off("GS_CHURN_LIST") &&
                        c.max_degree <= (gossip ? GSE_HOPS : CELL_W) && N < (1u << 21);
   // the push path with gossip or churn runs split, without tile skip
   // the push path with gossip or churn runs split + tile skip (its long tail of
   // IHAVE and churn buckets touches few tiles); GS_RELAX_VARIANT can turn the skip off
-  const uint32_t pvariant = (gossip || churn) ? (((variant | 8u) & ~32u) | (var_env && *var_env ? 0u : 2u))
+  const uint32_t pvariant = (gossip || churn) ? (((variant | 8u) & ~32u) | (var_env < 0 ? 2u : 0u))
                                               : (variant & ~32u);
   if (churn && !lanes32) c.fail(GS_EUNSUPPORTED, "churn needs peers*batch*FP < 2^32");
   std::vector<uint64_t> q0v(Bmax), r0v(Bmax), ep(churn ? n_msgs : 0);
@@ -1823,8 +1804,7 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
   // and when that fails (or failed before: glp_prefer) inside the group's passes
   // as run_glp does, if the whole group is lockstep (else single batches take
   // it). GS_SLICES=0 turns them off, GS_SLICES=n caps a group at n slices.
-  const char* sl_env = getenv("GS_SLICES");
-  const uint32_t sl_max = sl_env && *sl_env ? (uint32_t)std::max(0, atoi(sl_env)) : 64u;
+  const uint32_t sl_max = (uint32_t)std::max(0l, env_int("GS_SLICES", 64));
   constexpr uint64_t SL_ROWS = 1ull << 19;  // rows per pass a group aims at (memory: ~S x N x L x 40 B)
   uint64_t slice_skip = 0;                  // messages before it run as single batches
   auto try_slices = [&](uint64_t i0, uint64_t& i_end) -> bool {
@@ -1878,10 +1858,9 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
         lock = lock && rel[q] == rel[0];
       }
     }
-    const char* glp_env = getenv("GS_GOSSIP_LIST");
     Batch gg = g;
     gg.delta = std::min(g.delta, g.lat_min);
-    const bool glp_ok = lock && !(glp_env && *glp_env && atoi(glp_env) == 0) && c.max_degree <= GSE_HOPS &&
+    const bool glp_ok = lock && !env_off("GS_GOSSIP_LIST") && c.max_degree <= GSE_HOPS &&
                         gg.delta >= grain && c.cfg.heartbeat_ns > g.lat_max + gg.delta;
     if (gossip && c.glp_prefer && !glp_ok) return false;  // single batches (the push path)
     const size_t NR = (size_t)S * N;
@@ -2297,7 +2276,7 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
       ra.ctrl = c.d_ctrl.p;
       ra.counters = c.d_counters.p; ra.delta = b.delta;
       const uint64_t need = (total + TB - 1) / TB;
-      const unsigned grid = (unsigned)std::min<uint64_t>(need, (uint64_t)dev_cus * split_blocks_per_cu(c));
+      const unsigned grid = (unsigned)std::min<uint64_t>(need, (uint64_t)dev_cus * SPLIT_BLOCKS_PER_CU);
       if (v & 8) {  // frontier segments: one per scan wave
         const uint64_t nwaves = (uint64_t)grid * (TB / 64), ntiles = (total + 63) / 64;
         // tiles one scan wave can visit: groups of 64 with tile skip (k_scan), single tiles without
@@ -2395,8 +2374,7 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
     // own) wherever fragmented rows run at all (bit 128); GS_IDW_FRAG_LIST=0 keeps
     // them on the push path (A/B, per batch). With colliding fragments (defect D8)
     // only lane 0 of a group is ever final, as without IDONTWANT.
-    const char* ifl_env = getenv("GS_IDW_FRAG_LIST");
-    const bool idw_frag = (variant & 128) && !(ifl_env && *ifl_env && atoi(ifl_env) == 0);
+    const bool idw_frag = (variant & 128) && !env_off("GS_IDW_FRAG_LIST");
     const bool pull_ok = pull_any && bw.delta >= pull_grain(b.tshift) &&
                          (!idw_b || ((variant & 64) && (b.FP == 1 || idw_frag)));
     // Lazy gossip inside the list pass (GOS, gs_lpull_kernel.h): rows with or
@@ -2412,9 +2390,8 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
     Batch bg = b;
     bg.delta = std::min(b.delta, b.lat_min);
     const uint64_t ggr = pull_grain(b.tshift);
-    const char* glp_env = getenv("GS_GOSSIP_LIST");
     const bool glp = gossip && !churn && pull_ok && (b.FP == 1 || (variant & 128)) && (variant & 64) && lockstep &&
-                     !(glp_env && *glp_env && atoi(glp_env) == 0) && c.max_degree <= GSE_HOPS && bg.delta >= ggr &&
+                     !env_off("GS_GOSSIP_LIST") && c.max_degree <= GSE_HOPS && bg.delta >= ggr &&
                      c.cfg.heartbeat_ns > b.lat_max + bg.delta;
     bool glp_tried = false;
     auto run_glp = [&]() -> bool {
@@ -2520,9 +2497,8 @@ static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, 
         // needs the batch's deliveries and latest final time only (batch_sums). The passes'
         // 32-bit ms need every final time below 2^38 ns: checked on the batch's latest final
         // time after its passes (NoLog::inexact). GS_LPULL_SUM=0 (A/B, per batch): the log and k_lsum.
-        const char* nl_env = getenv("GS_LPULL_SUM");
         nl.on = K && !dense && !sw.lat && !idw_b && !churn && b.FP == 1 && (!gossip || lockstep) &&
-                !(nl_env && *nl_env && atoi(nl_env) == 0);
+                !env_off("GS_LPULL_SUM");
         bool lp_ok =
             K && run_lpull_batch(c, bw, K, lb, ev, n_ev, dev_cus, dense, idw_b, nullptr, nullptr, nullptr, &nl);
         if (!lp_ok && nl.inexact) {  // the same pass again with its log (k_lsum's 64-bit ms)

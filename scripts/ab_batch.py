@@ -1,6 +1,6 @@
 """A/B of list-pass shapes on the bench workload (1M peers, 1024 messages per
 round, one process, interleaved rounds): each config is `batch[:ENV=VAL,...]`,
-e.g.  python scripts/ab_batch.py --configs 1024 512 512:GS_LPULL_CH=16
+e.g.  python scripts/ab_batch.py --configs 1024 512 512:GS_LPULL_SUM=0
 Every config must give the same counters; prints ms per 1024 messages and the
 window-pass time (HIP events) per config."""
 import argparse
@@ -16,7 +16,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--peers", type=int, default=1_000_000)
 ap.add_argument("--rounds", type=int, default=4)
 ap.add_argument("--msgs", type=int, default=1024)
-ap.add_argument("--configs", nargs="+", default=["1024", "512", "512:GS_LPULL_CH=16"])
+ap.add_argument("--configs", nargs="+", default=["1024", "512", "512:GS_LPULL_SUM=0"])
 args = ap.parse_args()
 cfgs = []
 sims = {}

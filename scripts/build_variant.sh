@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B builds: libgossipsim_<name>.so = the in-tree objects with gs_relax.hip
-# recompiled under extra defines, e.g.  scripts/build_variant.sh ng8 -DGS_LP_NG=8 -DGS_LP_RCH=1
+# recompiled under extra defines, e.g.  scripts/build_variant.sh prof -DGS_PULL_PROF
 # SRC=<csrc dir> (e.g. a git archive of an older commit): every object is
 # built from that tree (headers such as gs_internal.h may differ between the
 # two builds, so objects of different trees never mix).

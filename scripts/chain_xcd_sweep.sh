@@ -1,6 +1,6 @@
 #!/bin/bash
-# Config #3 probe: the epoch chain, the churn tables (side stream) and the
-# passes on separate XCD sets (serial batch: the sum, each part's cost).
+# Config #3 probe: the epoch chain and the passes on separate XCD sets
+# (serial batch: the sum, each part's cost).
 set -u
 OUT=${OUT:-gpurun_out/chain_xcd}
 mkdir -p "$OUT"
@@ -11,13 +11,9 @@ while read -r envs; do
   echo "rc=$rc" >> "$OUT/sweep.txt"
   case $rc in 0) ;; *) echo "stop rc=$rc"; exit $rc;; esac
 done <<'LIST'
-GS_EV_SW=1
 GS_CHAIN_XCDS=0 GS_PASS_XCDS=1-7
 GS_CHAIN_XCDS=0 GS_PASS_XCDS=2-7
 GS_CHAIN_XCDS=0 GS_PASS_XCDS=3-7
 GS_CHAIN_XCDS=0 GS_PASS_XCDS=4-7
-GS_CHAIN_XCDS=0 GS_SIDE_XCDS=1-2 GS_PASS_XCDS=3-7
-GS_CHAIN_XCDS=0 GS_SIDE_XCDS=1 GS_PASS_XCDS=2-7
-GS_CHAIN_XCDS=0 GS_SIDE_XCDS=1-7
 LIST
 grep -E "==|c3 probe" "$OUT/sweep.txt"

@@ -1,4 +1,4 @@
-"""The list pass's streamed record step (gs_lpull_kernel.h, GS_LP_STREAM;
+"""The list pass's streamed record step (gs_lpull_kernel.h, STREAM;
 DESIGN.md §4.3): a row's neighbours stream their 64-record chunks through four
 contexts of two register slots each; a context whose neighbour is exhausted
 takes the row's next candidate. A wrong cursor, a refill with stale constants

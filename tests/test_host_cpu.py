@@ -692,3 +692,36 @@ def test_uplink_fifo_closed_form(tmp_path):
     subprocess.run(["g++", "-O2", "-o", str(exe), os.path.join(ROOT, "scripts", "fifo_check.cpp")], check=True)
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout
+
+
+def test_env_knobs_match_design_table():
+    """The GS_* variables the library reads (csrc/, gs_host.cpp's run
+    configuration aside) are exactly the rows of DESIGN.md §6.1, every knob is
+    read through getenv, xcd_env or gs_internal.h's env_off / env_int with its
+    name as a literal, and every row classed `test` is named by a test or by
+    bench.py."""
+    csrc = os.path.join(ROOT, "dst-libp2p-test-node_amd", "csrc")
+    read = set()
+    for path in sorted(glob.glob(os.path.join(csrc, "*"))):
+        if os.path.basename(path) == "gs_host.cpp":
+            continue
+        text = open(path).read()
+        read |= set(re.findall(r'\b(?:getenv|xcd_env|env_off|env_int)\(\s*"(GS_[A-Z0-9_]+)"', text))
+        # a name that is no literal: only inside the helpers themselves
+        for arg in re.findall(r"\bgetenv\(\s*([^\"\s][^)]*)\)", text):
+            assert arg == "name", "%s: getenv(%s)" % (os.path.basename(path), arg)
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    m = re.search(r"^### 6\.\d+ Environment knobs\n(.*?)^##", design, re.S | re.M)
+    assert m, "DESIGN.md §6 has no 'Environment knobs' subsection"
+    assert "Nothing outside this table changes what the library runs" in " ".join(m.group(1).split())
+    rows = re.findall(r"^\| `(GS_[A-Z0-9_]+)` \|[^|]+\| (\w+) \| (per (?:process|run|batch))[^|]*\|$", m.group(1), re.M)
+    table = {name: cls for name, cls, _ in rows}
+    assert len(table) == len(rows) == len(re.findall(r"^\| `", m.group(1), re.M)), "a malformed or repeated row"
+    assert set(table) == read, "only read: %s; only in the table: %s" % (sorted(read - set(table)),
+                                                                        sorted(set(table) - read))
+    assert set(table.values()) <= {"test", "diagnostic", "tuning"}
+    users = "".join(open(p).read() for p in sorted(glob.glob(os.path.join(ROOT, "tests", "*.py")))
+                    if os.path.basename(p) != "test_host_cpu.py")
+    users += open(os.path.join(ROOT, "bench.py")).read()
+    unused = sorted(k for k, cls in table.items() if cls == "test" and not re.search(r"\b%s\b" % k, users))
+    assert not unused, "classed `test` but named by no test nor bench.py: %s" % unused
