@@ -57,6 +57,11 @@ GS_HD uint64_t rng_pre(uint64_t seed, uint32_t purpose, uint32_t a) {
 GS_HD uint64_t rng_fin(uint64_t pre, uint32_t b, uint32_t c) {
   return mix64(pre ^ ((((uint64_t)b) << 32) | c) ^ 0xD6E8FEB86659FD93ull);
 }
+// The nim node's msgId = rand(high(int64)) (nim gossipsub-queues/main.nim:162) as a
+// 63-bit draw from (seed, publisher, t_pub): what its log lines carry.
+GS_HD uint64_t nim_msg_id(uint64_t seed, uint32_t publisher, uint64_t t_pub_ns) {
+  return rng(seed, P_MSGID, publisher, (uint32_t)(t_pub_ns >> 32), (uint32_t)t_pub_ns) >> 1;
+}
 GS_HD uint64_t mulhi64(uint64_t a, uint64_t b) {
 #if defined(__HIP_DEVICE_COMPILE__)
   return __umul64hi(a, b);

@@ -27,6 +27,13 @@ Ctx::~Ctx() {
     if (lat_done[k]) (void)hipEventDestroy(lat_done[k]);
     if (h_lat[k]) (void)hipHostFree(h_lat[k]);
   }
+  for (int k = 0; k < 2; k++) {
+    if (text_meta_ev[k]) (void)hipEventDestroy(text_meta_ev[k]);
+    if (text_fmt_ev[k]) (void)hipEventDestroy(text_fmt_ev[k]);
+    if (text_done_ev[k]) (void)hipEventDestroy(text_done_ev[k]);
+    if (h_text[k]) (void)hipHostFree(h_text[k]);
+  }
+  if (h_tmeta) (void)hipHostFree(h_tmeta);
   for (auto& v : cp_ev)
     for (auto e : v) (void)hipEventDestroy(e);
   if (pass_ms) (void)hipStreamDestroy(pass_ms);
@@ -248,6 +255,56 @@ extern "C" gs_status gs_run(gs_ctx* ctx, const gs_publish* sched, uint64_t n_msg
     ctx->fail(GS_EINVAL, "gs_result_sink: on_lat and GS_WANT_LAT_MS go together");
   GS_HIP(hipSetDevice(ctx->cfg.device));
   if (n_msgs) run_messages(*ctx, sched, n_msgs, sink);
+  GS_API_END(ctx)
+}
+
+// The arrival log as text (gs_logtext.h). gs_run_log runs gs_run with a latency-only
+// streaming sink — so the schedule order is kept (class_plan), every completion path writes
+// the u16 latencies and no batch runs without its log — whose on_lat is never called:
+// while ctx->text.fn is set, deliver hands each batch's latencies to the formatter.
+static void text_sink_unused(void*, uint64_t, uint32_t, uint32_t, const uint16_t*) {}
+struct TextCall {
+  gs_ctx* c;
+  TextCall(gs_ctx* ctx, const gs_publish* sched, gs_text_fn fn, void* user, uint64_t chunk) : c(ctx) {
+    c->text.fn = fn;
+    c->text.user = user;
+    c->text.chunk = chunk;
+    c->text.sched = sched;
+  }
+  ~TextCall() { c->text = Ctx::TextRun{}; }
+};
+
+extern "C" gs_status gs_run_log(gs_ctx* ctx, const gs_publish* sched, uint64_t n_msgs, gs_text_fn on_text,
+                                void* user, uint64_t chunk_bytes) {
+  GS_API_BEGIN(ctx)
+  if (!on_text) ctx->fail(GS_EINVAL, "gs_run_log: on_text is NULL");
+  if (!ctx->mesh_built) ctx->fail(GS_ESTATE, "gs_mesh_converge first");
+  if (!sched && n_msgs) ctx->fail(GS_EINVAL, "null schedule");
+  if (ctx->part_parts > 1) ctx->fail(GS_EUNSUPPORTED, "gs_run_log: not on a partitioned context");
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  TextCall call(ctx, sched, on_text, user, chunk_bytes);
+  gs_result_sink sink{};
+  sink.want = GS_WANT_LAT_MS;
+  sink.on_lat = text_sink_unused;
+  if (n_msgs) run_messages(*ctx, sched, n_msgs, &sink);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_format_lat_log(gs_ctx* ctx, const gs_publish* sched, uint64_t n_msgs, const uint16_t* lat_ms,
+                                       gs_text_fn on_text, void* user, uint64_t chunk_bytes) {
+  GS_API_BEGIN(ctx)
+  if (!on_text) ctx->fail(GS_EINVAL, "gs_format_lat_log: on_text is NULL");
+  if ((!sched || !lat_ms) && n_msgs) ctx->fail(GS_EINVAL, "null schedule or latencies");
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  TextCall call(ctx, sched, on_text, user, chunk_bytes);
+  if (n_msgs) format_lat_log(*ctx, sched, n_msgs, lat_ms);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_log_text_reset(gs_ctx* ctx) {
+  GS_API_BEGIN(ctx)
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  log_text_reset(*ctx);
   GS_API_END(ctx)
 }
 

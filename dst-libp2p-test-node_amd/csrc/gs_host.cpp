@@ -707,7 +707,7 @@ extern "C" gs_status gs_write_latency_log(const char* path, const gs_publish* sc
 // nim main.nim:150: msgId) in grep's path:line:text form (shadow/run.sh:61).
 namespace {
 uint64_t nim_msg_id(const gs_config* cfg, const gs_publish& p) {  // msgId = rand(high(int64)) (main.nim:162)
-  return gs::rng(cfg->seed, gs::P_MSGID, p.publisher, (uint32_t)(p.t_pub_ns >> 32), (uint32_t)p.t_pub_ns) >> 1;
+  return gs::nim_msg_id(cfg->seed, p.publisher, p.t_pub_ns);
 }
 void log_line_ms(FILE* f, const gs_config* cfg, uint32_t u, uint64_t line, const gs_publish& p, int64_t ms) {
   if (cfg->node == GS_NODE_NIM)
@@ -768,6 +768,18 @@ extern "C" gs_status gs_log_write_lat(gs_log* L, const gs_publish* sched, uint32
       log_line_ms(L->f, &L->cfg, u, ++L->line[u], sched[m], (int64_t)v);
     }
   return ferror(L->f) ? GS_EINVAL : GS_OK;
+}
+
+// The longest line log_line_ms can print for cfg: the constant text (57 bytes), the
+// largest peer id, a u32 line number, the id ("%lld" of an int64: 20 characters with
+// its sign; a 63-bit nim msgId: 19 digits) and a u16 ms. The device formatter
+// (gs_logtext.h) sizes its buffers with the same count.
+extern "C" uint32_t gs_log_line_max(const gs_config* cfg) {
+  if (!cfg) return 0;
+  uint32_t dpeer = 1;
+  for (uint32_t v = cfg->peers ? cfg->peers - 1 : 0; v >= 10; v /= 10) dpeer++;
+  const uint32_t fixed = 22 + 18 + 1 + 15 + 1;  // path head, "/main.1000.stdout:", ':', " milliseconds: ", '\n'
+  return fixed + dpeer + 10 + (cfg->node == GS_NODE_NIM ? 19 : 20) + 5;
 }
 
 extern "C" gs_status gs_log_close(gs_log* L) {

@@ -210,6 +210,30 @@ struct Ctx {
     const gs_result_sink* sink = nullptr;
   } lat_pend;
   uint32_t lat_par = 0;
+  // the arrival log as text (gs_logtext.h; gs_run_log, gs_format_lat_log): the callback of the
+  // call in progress (fn set = deliver hands a batch's latencies to the formatter), the
+  // per-peer line counters, a chunk's line numbers / group sums / group offsets / ids, and
+  // the two device and pinned text buffers with their events
+  struct TextRun {
+    gs_text_fn fn = nullptr;
+    void* user = nullptr;
+    uint64_t chunk = 0;
+    const gs_publish* sched = nullptr;
+  } text;
+  DevBuf<uint32_t> d_tcnt;   // [N]
+  DevBuf<uint32_t> d_tln;    // [chunk msgs][N]
+  DevBuf<uint32_t> d_tgsum;  // [chunk msgs][(N + 63) / 64]
+  DevBuf<uint64_t> d_tgoff;
+  DevBuf<uint8_t> d_tids;    // [B][24]
+  DevBuf<uint64_t> d_tmeta;  // [4] bytes, lines, counter overflow
+  DevBuf<char> d_text[2];
+  char* h_text[2] = {nullptr, nullptr};
+  size_t h_text_bytes[2] = {0, 0};
+  uint64_t* h_tmeta = nullptr;  // pinned [2][4]
+  hipEvent_t text_meta_ev[2] = {nullptr, nullptr}, text_fmt_ev[2] = {nullptr, nullptr},
+             text_done_ev[2] = {nullptr, nullptr};
+  uint32_t text_par = 0;
+  bool text_busy = false;
   DevBuf<uint32_t> d_tables; // lat[S*S] | ser_up[S] | ser_dn[S] (u32 ns)
   DevBuf<uint64_t> d_ctrl;   // [4] triple-buffered next-min keys + spare
   // owner-computes pull path (gs_pull_kernel.h)
@@ -352,6 +376,9 @@ void ensure_ring_ell(Ctx& c, uint64_t h0, uint64_t h1);
 hipStream_t side_stream(Ctx& c);
 void run_messages(Ctx& c, const gs_publish* sched, uint64_t n_msgs, const gs_result_sink* sink);
 void deliver_rows(Ctx& c, uint32_t B, uint32_t un, const gs_result_sink* sink, uint64_t sink_row0);
+// the arrival log as text (gs_logtext.h): c.text holds the callback
+void format_lat_log(Ctx& c, const gs_publish* sched, uint64_t n_msgs, const uint16_t* lat_ms);
+void log_text_reset(Ctx& c);
 void part_set(Ctx& c, uint32_t parts, uint32_t part);
 uint64_t part_begin(Ctx& c, const gs_publish* sched, uint64_t n_msgs);
 bool part_scan(Ctx& c, uint64_t bucket_key, gs_part_record* rec, uint64_t cap, uint64_t* n, uint64_t* m1);

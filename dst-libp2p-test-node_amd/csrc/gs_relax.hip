@@ -806,6 +806,8 @@ static void deliver_lat_async(Ctx& c, const Batch& b, uint32_t un, const gs_resu
   p.sink = sink;
 }
 
+#include "gs_logtext.h"
+
 // Results of a completed batch (peer-major d_tc / d_hops / d_lat of peers
 // [u0, u0 + un)) into the sink: transposed to message-major, copied out,
 // summaries.
@@ -816,6 +818,10 @@ static void deliver(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, const gs_r
   const SinkWants w = sink_wants(sink);
   if (c.keys_none && (w.rows() || w.lat || w.summary))
     c.fail(GS_EINVAL, "internal: a sink's results after a no-log list pass");
+  if (c.text.fn) {  // gs_run_log: the latencies leave as text (its sink asks for nothing else)
+    deliver_text(c, b, u0, un, sink_row0);
+    return;
+  }
   if (c.lat_async && w.lat && !w.rows() && !w.summary && sink->on_lat) {
     deliver_lat_async(c, b, un, sink, sink_row0);
     return;

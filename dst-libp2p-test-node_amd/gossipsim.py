@@ -62,6 +62,7 @@ class GsMsgSummary(ctypes.Structure):
 
 BLOCK_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, u64, u32, u32, P(u64), P(u8))
 LAT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, u64, u32, u32, P(ctypes.c_uint16))
+TEXT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, u64, u32, ctypes.c_void_p, u64, u64)  # gs_text_fn
 
 
 class GsResultSink(ctypes.Structure):
@@ -134,6 +135,11 @@ SIGNATURES = {
     "gs_mesh_converge": (i32, [ctypes.c_void_p, u32, P(u32)]),
     "gs_get_mesh": (i32, [ctypes.c_void_p, P(u32), P(u8)]),
     "gs_run": (i32, [ctypes.c_void_p, P(GsPublish), u64, P(GsResultSink)]),
+    "gs_run_log": (i32, [ctypes.c_void_p, P(GsPublish), u64, TEXT_FN, ctypes.c_void_p, u64]),
+    "gs_format_lat_log": (i32, [ctypes.c_void_p, P(GsPublish), u64, P(ctypes.c_uint16), TEXT_FN, ctypes.c_void_p,
+                                u64]),
+    "gs_log_text_reset": (i32, [ctypes.c_void_p]),
+    "gs_log_line_max": (u32, [P(GsConfig)]),
     "gs_get_stats": (i32, [ctypes.c_void_p, P(GsStats)]),
     "gs_get_config": (i32, [ctypes.c_void_p, P(GsConfig)]),
     "gs_save_state": (i32, [ctypes.c_void_p, ctypes.c_char_p]),
@@ -185,6 +191,11 @@ class GossipSimError(RuntimeError):
 
 def _ptr(a, ct):
     return a.ctypes.data_as(P(ct))
+
+
+def log_line_max(cfg):
+    """The longest arrival-log line `cfg` (a PeerConfig) can produce, in bytes (gs_log_line_max)."""
+    return int(lib().gs_log_line_max(ctypes.byref(cfg.c)))
 
 
 def wire_bytes(payload, muxer="yamux", signed=True):
@@ -565,6 +576,59 @@ class Simulator:
                 "max_ms": np.array([x.max_ms for x in sm], np.uint32),
                 "hist": np.array([list(x.hist) for x in sm], np.uint32).reshape(M, HIST_BINS)}
         return res
+
+    def _text_call(self, call, on_text, path):
+        """One gs_run_log / gs_format_lat_log call: `call(cb)` with the gs_text_fn for on_text
+        or the file at `path` (neither: NULL, which the library refuses). -> lines handed out."""
+        total = [0]
+        f = open(path, "wb", buffering=0) if path is not None else None
+        err = []
+
+        def _tcb(user, first, n, text, nbytes, lines):
+            total[0] += lines
+            try:
+                buf = (ctypes.c_char * nbytes).from_address(text) if nbytes else b""
+                if f is not None:
+                    f.write(buf)
+                if on_text is not None:
+                    on_text(int(first), int(n), bytes(buf), int(lines))
+            except BaseException as e:  # (no exception crosses the C frames)
+                err.append(e)
+
+        cb = TEXT_FN(_tcb) if (on_text is not None or f is not None) else TEXT_FN()
+        try:
+            self._check(call(cb))
+        finally:
+            if f is not None:
+                f.close()
+        if err:
+            raise err[0]
+        return total[0]
+
+    def run_log(self, schedule=None, on_text=None, path=None, chunk_bytes=0):
+        """gs_run_log: simulate like run(), the only output being the arrival log's text,
+        formatted on the device: written to `path`, and / or handed to
+        on_text(first_msg, n_msgs, text_bytes, lines) chunk by chunk (whole messages,
+        at most chunk_bytes each; 0 = the default). The chunks in order are byte for
+        byte what LogStream.write_lat writes for run(on_lat=...). -> lines written."""
+        schedule = self._schedule(schedule)
+        return self._text_call(
+            lambda cb: lib().gs_run_log(self.ctx, schedule, len(schedule), cb, None, chunk_bytes), on_text, path)
+
+    def format_lat_log(self, schedule, lat_ms, on_text=None, path=None, chunk_bytes=0):
+        """gs_format_lat_log: the same text from a stored latency stream lat_ms[M, N]
+        uint16 (LAT_NONE = no line); needs no topology. -> lines written."""
+        schedule = self._schedule(schedule)
+        lat = np.ascontiguousarray(lat_ms, np.uint16)
+        if lat.shape != (len(schedule), self.peers):
+            raise GossipSimError(GS_EINVAL, "lat_ms must be [len(schedule), peers]")
+        return self._text_call(
+            lambda cb: lib().gs_format_lat_log(self.ctx, schedule, len(schedule), _ptr(lat, ctypes.c_uint16), cb, None,
+                                               chunk_bytes), on_text, path)
+
+    def log_text_reset(self):
+        """Zero the per-peer line counters run_log / format_lat_log carry across calls."""
+        self._check(lib().gs_log_text_reset(self.ctx))
 
     def stats(self):
         st = GsStats()

@@ -24,8 +24,10 @@ void usage() {
           "usage: gossipsim-node [-bl MBIT] [-bh MBIT] [-ll MS] [-lh MS] [-st STAGES] [--shortest]\n"
           "         [-s MSG_BYTES] [-m MESSAGES] [--publisher ID] [--rotation 0|1]\n"
           "         [--delay-ms MS] [--t0-s SECONDS] [--http-us US] [--max-heartbeats H] [--latencies PATH]\n"
+          "         [--device-log]\n"
           "         [--gml network_topology.gml --yaml shadow.yaml] [--schedule FILE] [--shadowlog PATH] [--metrics PATH]\n"
           "  --yaml also supplies the injector's -s/-m/-d and start_time unless given on the command line\n"
+          "  --device-log writes --latencies from the device-formatted text (gs_run_log), one fwrite per chunk\n"
           "env: PEERS CONNECTTO FRAGMENTS MUXER MAXCONNECTIONS GOSSIPSUB_* SELFTRIGGER GS_NODE GS_SEED GS_BATCH\n"
           "     GS_DEVICE\n");
 }
@@ -74,6 +76,19 @@ void on_block(void* user, uint64_t first, uint32_t n, uint32_t peers, const uint
   }
 }
 
+// --device-log: the log's text arrives formatted (gs_run_log), one fwrite per chunk.
+struct TextOut {
+  FILE* f = nullptr;
+  bool ok = true;
+  uint64_t lines = 0;
+};
+
+void on_text(void* user, uint64_t, uint32_t, const char* text, uint64_t bytes, uint64_t lines) {
+  TextOut* T = (TextOut*)user;
+  if (bytes && fwrite(text, 1, (size_t)bytes, T->f) != bytes) T->ok = false;
+  T->lines += lines;
+}
+
 // nearest-rank percentile (rank ceil(q*n)) of the 1 ms histogram
 uint64_t pct(const std::vector<uint64_t>& h, uint64_t n, uint32_t q100) {
   const uint64_t rank = (n * q100 + 99) / 100;
@@ -100,7 +115,7 @@ int main(int argc, char** argv) {
   // after the injector sends it (topogen.py:64-69); tx_time is stamped then
   uint64_t http_us = 3000;
   std::string latencies, gml, yaml, shadowlog, metrics, schedule;
-  bool set_size = false, set_msgs = false, set_delay = false, set_t0 = false;
+  bool set_size = false, set_msgs = false, set_delay = false, set_t0 = false, device_log = false;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&](void) -> const char* {
@@ -122,6 +137,7 @@ int main(int argc, char** argv) {
     else if (a == "--http-us") http_us = strtoull(next(), nullptr, 10);
     else if (a == "--max-heartbeats") max_hb = (uint32_t)atoi(next());
     else if (a == "--latencies") latencies = next();
+    else if (a == "--device-log") device_log = true;  // --latencies from gs_run_log's text
     else if (a == "--gml") gml = next();            // a Shadow experiment's network graph ...
     else if (a == "--yaml") yaml = next();          // ... and its host placement (topogen.py output)
     else if (a == "--shadowlog") shadowlog = next(); // tracker counters for summary_shadowlog.awk
@@ -195,15 +211,30 @@ int main(int argc, char** argv) {
   Stream strm;
   strm.sched = sched.data();
   strm.self_log = cfg.self_log != 0;
-  if (!latencies.empty() && (st = gs_log_open(&cfg, latencies.c_str(), &strm.log)) != GS_OK)
+  bool text_done = false, wide_only = false;
+  if (device_log && !latencies.empty()) {  // the log formatted on the device, written as it arrives
+    TextOut out;
+    if (!(out.f = fopen(latencies.c_str(), "w"))) return die(ctx, GS_EINVAL, "fopen --latencies");
+    st = gs_run_log(ctx, sched.data(), n_msgs, on_text, &out, 0);
+    if (fclose(out.f) || !out.ok) return die(ctx, GS_EINVAL, "fwrite --latencies");
+    if (st == GS_OK) {
+      text_done = true;
+    } else if (st == GS_ERANGE) {  // as below: the run again through the completion times
+      wide_only = true;
+      gs_log_text_reset(ctx);
+    } else {
+      return die(ctx, st, "gs_run_log");
+    }
+  }
+  if (!text_done && !latencies.empty() && (st = gs_log_open(&cfg, latencies.c_str(), &strm.log)) != GS_OK)
     return die(ctx, st, "gs_log_open");
   gs_result_sink sink{};
   sink.want = GS_WANT_LAT_MS;  // the logged latency, streamed through on_lat
   sink.on_lat = on_lat;
   sink.user = &strm;
   sink.block_msgs = 16;
-  st = gs_run(ctx, sched.data(), n_msgs, &sink);
-  if (st == GS_ERANGE && strstr(gs_last_error(ctx), "GS_WANT_LAT_MS")) {
+  if (!text_done && !wide_only) st = gs_run(ctx, sched.data(), n_msgs, &sink);
+  if (wide_only || (st == GS_ERANGE && strstr(gs_last_error(ctx), "GS_WANT_LAT_MS"))) {
     // a latency the u16 stream cannot carry: the same run again (it is
     // deterministic) through the u64 completion times, the log from the start
     if (strm.log) gs_log_close(strm.log);
@@ -227,13 +258,23 @@ int main(int argc, char** argv) {
   gs_get_stats(ctx, &s);
   uint64_t n = 0;
   for (uint64_t c : strm.hist_ms) n += c;
-  fprintf(stderr,
-          "peers=%u mesh_epochs=%u messages=%llu deliveries=%llu frag_deliveries=%llu "
-          "relaxations=%llu gossip_iwant=%llu latency_ms p50=%llu p95=%llu max=%llu\n",
-          cfg.peers, epochs, (unsigned long long)s.messages, (unsigned long long)s.deliveries,
-          (unsigned long long)s.frag_deliveries, (unsigned long long)s.relaxations,
-          (unsigned long long)s.gossip_iwant, (unsigned long long)pct(strm.hist_ms, n, 50),
-          (unsigned long long)pct(strm.hist_ms, n, 95), (unsigned long long)pct(strm.hist_ms, n, 100));
+  if (text_done)  // no latency reached the host: the counters' mean and max
+    fprintf(stderr,
+            "peers=%u mesh_epochs=%u messages=%llu deliveries=%llu frag_deliveries=%llu "
+            "relaxations=%llu gossip_iwant=%llu latency_ms mean=%llu max=%llu\n",
+            cfg.peers, epochs, (unsigned long long)s.messages, (unsigned long long)s.deliveries,
+            (unsigned long long)s.frag_deliveries, (unsigned long long)s.relaxations,
+            (unsigned long long)s.gossip_iwant,
+            (unsigned long long)(s.deliveries ? s.latency_sum_ms / s.deliveries : 0),
+            (unsigned long long)s.latency_max_ms);
+  else
+    fprintf(stderr,
+            "peers=%u mesh_epochs=%u messages=%llu deliveries=%llu frag_deliveries=%llu "
+            "relaxations=%llu gossip_iwant=%llu latency_ms p50=%llu p95=%llu max=%llu\n",
+            cfg.peers, epochs, (unsigned long long)s.messages, (unsigned long long)s.deliveries,
+            (unsigned long long)s.frag_deliveries, (unsigned long long)s.relaxations,
+            (unsigned long long)s.gossip_iwant, (unsigned long long)pct(strm.hist_ms, n, 50),
+            (unsigned long long)pct(strm.hist_ms, n, 95), (unsigned long long)pct(strm.hist_ms, n, 100));
   if (counters) {
     std::vector<uint64_t> tr((size_t)cfg.peers * GS_TRAFFIC_COLS), row((size_t)cfg.peers + 1);
     std::vector<uint8_t> mc(cfg.peers);

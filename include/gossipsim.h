@@ -427,6 +427,36 @@ gs_status gs_get_mesh(struct gs_ctx* ctx, uint32_t* mesh, uint8_t* count);
 gs_status gs_run(struct gs_ctx* ctx, const gs_publish* sched, uint64_t n_msgs,
                  const gs_result_sink* sink);
 
+/* Device-formatted arrival log: `text` holds `bytes` bytes = `lines` whole lines of the
+ * messages [first_msg, first_msg + n_msgs), valid only during the call. The concatenation
+ * of all calls of a run, in call order, is byte for byte what gs_log_write_lat writes for
+ * the same run's on_lat stream (gs_log_open on a context-fresh counter state). */
+typedef void (*gs_text_fn)(void* user, uint64_t first_msg, uint32_t n_msgs,
+                           const char* text, uint64_t bytes, uint64_t lines);
+
+/* gs_run whose only output is the log text (replaces the println! of main.rs:93 and the
+ * grep of shadow/run.sh:61 at once). chunk_bytes: text bytes per callback at most
+ * (0 = default, 256 MB; raised to one message's bound, peers x the longest line). The
+ * callback of one chunk runs while the next is formatted and copied. Counters in
+ * gs_stats as gs_run. GS_ERANGE: a latency of 65535 ms or more (before any text of that
+ * batch is handed out), or a peer's line counter passing 2^32 - 1. */
+gs_status gs_run_log(struct gs_ctx*, const gs_publish* sched, uint64_t n_msgs,
+                     gs_text_fn on_text, void* user, uint64_t chunk_bytes);
+
+/* The same formatter over a caller's u16 array lat_ms[n_msgs][peers] (an archived on_lat
+ * stream): needs only gs_create, no graph. */
+gs_status gs_format_lat_log(struct gs_ctx*, const gs_publish* sched, uint64_t n_msgs,
+                            const uint16_t* lat_ms, gs_text_fn on_text, void* user,
+                            uint64_t chunk_bytes);
+
+/* Per-peer line counters: zero at gs_create, carried across gs_run_log / gs_format_lat_log
+ * calls (as one gs_log carries them across gs_log_write_lat calls); this zeroes them.
+ * After a failed call they are unspecified until this call. */
+gs_status gs_log_text_reset(struct gs_ctx*);
+
+/* Host-only: the longest line cfg can produce, in bytes (sizes the buffers). */
+uint32_t gs_log_line_max(const gs_config* cfg);
+
 gs_status gs_get_stats(const struct gs_ctx* ctx, gs_stats* out);
 gs_status gs_reset_stats(struct gs_ctx* ctx);
 

@@ -44,6 +44,8 @@ pub type gs_block_fn = Option<unsafe extern "C" fn(user: *mut c_void, first_msg:
                                                    t_complete_ns: *const u64, hops: *const u8)>;
 pub type gs_lat_fn = Option<unsafe extern "C" fn(user: *mut c_void, first_msg: u64, n_msgs: u32, peers: u32,
                                                  lat_ms: *const u16)>;
+pub type gs_text_fn = Option<unsafe extern "C" fn(user: *mut c_void, first_msg: u64, n_msgs: u32, text: *const c_char,
+                                                  bytes: u64, lines: u64)>;
 #[repr(C)]
 pub struct gs_result_sink {
     pub t_complete_ns: *mut u64, pub hops: *mut u8, pub on_block: gs_block_fn, pub user: *mut c_void,
@@ -124,6 +126,12 @@ extern "C" {
     pub fn gs_mesh_converge(ctx: *mut gs_ctx, max_heartbeats: u32, epochs: *mut u32) -> gs_status;
     pub fn gs_get_mesh(ctx: *mut gs_ctx, mesh: *mut u32, count: *mut u8) -> gs_status;
     pub fn gs_run(ctx: *mut gs_ctx, sched: *const gs_publish, n: u64, sink: *const gs_result_sink) -> gs_status;
+    pub fn gs_run_log(ctx: *mut gs_ctx, sched: *const gs_publish, n: u64, on_text: gs_text_fn, user: *mut c_void,
+                      chunk_bytes: u64) -> gs_status;
+    pub fn gs_format_lat_log(ctx: *mut gs_ctx, sched: *const gs_publish, n: u64, lat_ms: *const u16,
+                             on_text: gs_text_fn, user: *mut c_void, chunk_bytes: u64) -> gs_status;
+    pub fn gs_log_text_reset(ctx: *mut gs_ctx) -> gs_status;
+    pub fn gs_log_line_max(cfg: *const gs_config) -> u32;
     pub fn gs_get_stats(ctx: *const gs_ctx, out: *mut gs_stats) -> gs_status;
     pub fn gs_reset_stats(ctx: *mut gs_ctx) -> gs_status;
     pub fn gs_set_timing(ctx: *mut gs_ctx, enable: u32) -> gs_status;
