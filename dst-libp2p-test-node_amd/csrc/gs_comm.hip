@@ -378,9 +378,10 @@ void rank_status(gs_comm* cm, Ctx& c, uint64_t mine) {
 // Every RCCL rank must run the same protocol: the knobs that decide the
 // batches and the collectives they enter are compared across ranks (MIN and
 // MAX of each word agree) before the first batch.
-void check_same_config(gs_comm* cm, Ctx& c, const gs_publish* sched, uint64_t n_msgs) {
+void check_same_config(gs_comm* cm, Ctx& c, const gs_publish* sched, uint64_t n_msgs, uint64_t lat) {
   if (cm->local) return;
-  uint64_t h = 1469598103934665603ull;  // FNV-1a over the schedule
+  // FNV-1a over the schedule, and whether the sink takes the u16 latencies (lat_gate's collective)
+  uint64_t h = (1469598103934665603ull ^ lat) * 1099511628211ull;
   for (uint64_t i = 0; i < n_msgs; i++) {
     const uint64_t v[4] = {sched[i].t_pub_ns, sched[i].publisher, sched[i].msg_size, sched[i].frags};
     for (uint64_t x : v) h = (h ^ x) * 1099511628211ull;
@@ -399,7 +400,7 @@ void check_same_config(gs_comm* cm, Ctx& c, const gs_publish* sched, uint64_t n_
   for (int k = 0; k < 8; k++)
     if (c.h_pinned[k] != c.h_pinned[8 + k])
       throw Error(GS_EINVAL, "RCCL ranks disagree on the partitioned run (peers, batch, lazy_gossip, idontwant, "
-                             "churn, fragments, seed or schedule)");
+                             "churn, fragments, seed, schedule or the latency stream)");
 }
 
 // RCCL ranks: every rank's n words (n <= 4) -> out[rank * n + k] on the host.
@@ -412,6 +413,42 @@ void rank_gather(gs_comm* cm, Ctx& c, const uint64_t* mine, uint32_t n, uint64_t
   GS_HIP(hipMemcpyAsync(h.data(), w, h.size() * 8, hipMemcpyDeviceToHost, c.stream));
   GS_HIP(hipStreamSynchronize(c.stream));
   memcpy(out, h.data(), h.size() * 8);
+}
+
+// The u16 latencies of a batch (a sink's on_lat, or the log's text) leave only when no part
+// and no rank failed the batch: the staged parts' error words (part_lat_stage), combined over
+// the ranks with the pass control's all-gather, before the first hand-over. Every rank then
+// fails the call alike, and none is left waiting in the next batch's collectives.
+bool wants_lat(const gs_result_sink* sinks, uint32_t i) { return sinks && sinks[i].on_lat; }
+
+void lat_gate(gs_comm* cm, Ctx** cx, uint32_t nctx) {
+  uint64_t err = 0;
+  for (uint32_t i = 0; i < nctx; i++) {
+    if (!cx[i]->lat_staged) continue;
+    GS_HIP(hipSetDevice(cx[i]->cfg.device));
+    err |= part_lat_err(*cx[i]);
+  }
+  if (!cm->local) {
+    uint64_t all[64];
+    rank_gather(cm, *cx[0], &err, 1, all);
+    for (uint32_t k = 0; k < cm->nranks; k++) err |= all[k];
+  }
+  if (err & ERR_LAT16)
+    throw Error(GS_ERANGE, "a logged latency of 65535 ms or more does not fit the u16 latencies (GS_WANT_LAT_MS, "
+                           "the arrival log's text)");
+  if (err) throw Error(GS_ERANGE, "arrival log: a peer's line counter would pass 2^32 - 1");
+}
+
+// Every part that hands out latencies stages the finished peer-protocol batch, then the gate.
+void lat_stage_all(gs_comm* cm, Ctx** cx, uint32_t nctx, const gs_result_sink* sinks, uint32_t B) {
+  bool any = false;
+  for (uint32_t i = 0; i < nctx; i++) {
+    if (!wants_lat(sinks, i)) continue;
+    GS_HIP(hipSetDevice(cx[i]->cfg.device));
+    part_lat_stage(*cx[i], B, nullptr);
+    any = true;
+  }
+  if (any) lat_gate(cm, cx, nctx);
 }
 
 // Message-sharded batch: the batches the peer protocols
@@ -448,17 +485,21 @@ void run_batch_ms(gs_comm* cm, Ctx** cx, uint32_t nctx, const gs_publish* sched,
         ds.t_complete_ns = c.d_ms_tc.p;
         ds.hops = c.d_ms_hops.p;
         const uint32_t batch = c.cfg.batch;
+        const Ctx::TextRun text = c.text;
         c.cfg.batch = mpmax;  // buffers for this part's share, not the whole batch
         c.sink_dev = true;
+        c.text = Ctx::TextRun{};  // (the log's text is of the own peers' rows, after the exchange)
         try {
           run_messages(c, sched + i0 + m0, mp, &ds);
         } catch (...) {
           c.cfg.batch = batch;
           c.sink_dev = false;
+          c.text = text;
           throw;
         }
         c.cfg.batch = batch;
         c.sink_dev = false;
+        c.text = text;
       }
       c.stats.messages += B - mp;  // every part counts the batch, as in the peer protocols
       c.stats.batches = batches + 1;
@@ -531,13 +572,23 @@ void run_batch_ms(gs_comm* cm, Ctx** cx, uint32_t nctx, const gs_publish* sched,
     coll_group_end(cm);
     GS_HIP(hipStreamSynchronize(c.stream));
   }
-  // 3. own peers' rows into the sinks
+  // 3. own peers' rows into the sinks; the logged latencies of them from the exchanged
+  // completion times (k_lat_rows), every part's before the gate and the first hand-over
   if (!sinks) return;
+  bool any = false;
+  for (uint32_t i = 0; i < nctx; i++) {
+    if (!wants_lat(sinks, i)) continue;
+    GS_HIP(hipSetDevice(cx[i]->cfg.device));
+    part_lat_stage(*cx[i], B, sched + i0);
+    any = true;
+  }
+  if (any) lat_gate(cm, cx, nctx);
   for (uint32_t i = 0; i < nctx; i++) {
     Ctx& c = *cx[i];
     const uint32_t me = cm->local ? i : cm->rank, un = lay.un(me);
     GS_HIP(hipSetDevice(c.cfg.device));
-    deliver_rows(c, B, un, &sinks[i], i0);
+    if (wants_lat(sinks, i)) part_lat_deliver_ms(c, B, &sinks[i], i0);
+    else deliver_rows(c, B, un, &sinks[i], i0);
     GS_HIP(hipStreamSynchronize(c.stream));
   }
 }
@@ -853,6 +904,7 @@ bool run_batch_lp(gs_comm* cm, Ctx** cx, uint32_t nctx, const gs_publish* sched,
     gossip_to_ms(cm, cx, nctx, sched, i0, B, sinks);
     return true;
   }
+  lat_stage_all(cm, cx, nctx, sinks, B);
   for (uint32_t i = 0; i < nctx; i++) {
     GS_HIP(hipSetDevice(cx[i]->cfg.device));
     part_dev_finish(*cx[i], sinks ? &sinks[i] : nullptr, i0);
@@ -1040,7 +1092,7 @@ void run_batch(gs_comm* cm, Ctx** cx, uint32_t nctx, const gs_publish* sched, ui
   bool ok = true;
   for (uint32_t i = 0; i < nctx; i++) {
     GS_HIP(hipSetDevice(cx[i]->cfg.device));
-    ok = part_dev_complete(*cx[i], sinks && sinks[i].summary) && ok;
+    ok = part_dev_complete(*cx[i], sinks && sinks[i].summary, true, wants_lat(sinks, i)) && ok;
   }
   if (!cm->local && cx[0]->cfg.lazy_gossip) {
     Ctx& c = *cx[0];
@@ -1055,26 +1107,31 @@ void run_batch(gs_comm* cm, Ctx** cx, uint32_t nctx, const gs_publish* sched, ui
     gossip_to_ms(cm, cx, nctx, sched, i0, B, sinks);
     return;
   }
+  lat_stage_all(cm, cx, nctx, sinks, B);
   for (uint32_t i = 0; i < nctx; i++) {
     GS_HIP(hipSetDevice(cx[i]->cfg.device));
     part_dev_finish(*cx[i], sinks ? &sinks[i] : nullptr, i0);
   }
 }
 
-}  // namespace
-
-extern "C" gs_status gs_run_partitioned(gs_ctx* const* ctxs, uint32_t nctx, gs_comm* comm, const gs_publish* sched,
-                                        uint64_t n_msgs, const gs_result_sink* sinks) {
-  if (!ctxs || !nctx || !comm || (!sched && n_msgs)) return GS_EINVAL;
-  for (uint32_t i = 0; i < nctx; i++)
-    if (!ctxs[i]) return GS_EINVAL;
+// gs_run_partitioned's body; gs_run_partitioned_log calls it with latency-only sinks while
+// every context's text callback is set (Ctx::text, as gs_run_log).
+gs_status run_partitioned(gs_ctx* const* ctxs, uint32_t nctx, gs_comm* comm, const gs_publish* sched, uint64_t n_msgs,
+                          const gs_result_sink* sinks) {
   Ctx* c0 = ctxs[0];
   try {
     if (comm->local ? nctx != comm->nranks : nctx != 1)
       c0->fail(GS_EINVAL, "gs_run_partitioned: pass one context per part (local) or this rank's context (RCCL)");
-    for (uint32_t i = 0; sinks && i < nctx; i++)
-      if (sinks[i].on_lat || (sinks[i].want & GS_WANT_LAT_MS))
-        c0->fail(GS_EUNSUPPORTED, "gs_run_partitioned: the u16 latency stream (on_lat) is gs_run's");
+    for (uint32_t i = 0; sinks && i < nctx; i++) {  // gs_run's rules, for every part's sink
+      const gs_result_sink& k = sinks[i];
+      if (k.on_block && (k.t_complete_ns || k.hops))
+        c0->fail(GS_EINVAL, "gs_result_sink: with on_block, t_complete_ns and hops must be NULL (select outputs "
+                            "with want, ABI 7)");
+      if (k.want & ~(uint32_t)(GS_WANT_T_COMPLETE | GS_WANT_HOPS | GS_WANT_LAT_MS))
+        c0->fail(GS_EINVAL, "gs_result_sink.want: unknown bits");
+      if ((k.on_lat != nullptr) != ((k.want & GS_WANT_LAT_MS) != 0))
+        c0->fail(GS_EINVAL, "gs_result_sink: on_lat and GS_WANT_LAT_MS go together");
+    }
     std::vector<Ctx*> cx(nctx);
     for (uint32_t i = 0; i < nctx; i++) {
       cx[i] = ctxs[i];
@@ -1086,7 +1143,7 @@ extern "C" gs_status gs_run_partitioned(gs_ctx* const* ctxs, uint32_t nctx, gs_c
     }
     if (!comm->local && c0->cfg.device != comm->device)
       c0->fail(GS_EINVAL, "the context and the communicator must use the same device");
-    check_same_config(comm, *c0, sched, n_msgs);
+    check_same_config(comm, *c0, sched, n_msgs, wants_lat(sinks, 0) ? 1 : 0);
     uint64_t i0 = 0;
     while (i0 < n_msgs) {  // batches of equal size and chunk count, at most cfg.batch messages
       uint64_t i1 = i0 + 1;
@@ -1106,4 +1163,44 @@ extern "C" gs_status gs_run_partitioned(gs_ctx* const* ctxs, uint32_t nctx, gs_c
     return GS_ENOMEM;
   }
   return GS_OK;
+}
+
+void text_sink_unused(void*, uint64_t, uint32_t, uint32_t, const uint16_t*) {}
+
+}  // namespace
+
+extern "C" gs_status gs_run_partitioned(gs_ctx* const* ctxs, uint32_t nctx, gs_comm* comm, const gs_publish* sched,
+                                        uint64_t n_msgs, const gs_result_sink* sinks) {
+  if (!ctxs || !nctx || !comm || (!sched && n_msgs)) return GS_EINVAL;
+  for (uint32_t i = 0; i < nctx; i++)
+    if (!ctxs[i]) return GS_EINVAL;
+  return run_partitioned(ctxs, nctx, comm, sched, n_msgs, sinks);
+}
+
+// The arrival log's text of a partitioned run (gs_logtext.h): gs_run_partitioned with a
+// latency-only sink per part, whose on_lat is never called: while a context's text callback
+// is set, its batches' latencies go to the formatter over the part's own peer range.
+extern "C" gs_status gs_run_partitioned_log(gs_ctx* const* ctxs, uint32_t nctx, gs_comm* comm, const gs_publish* sched,
+                                            uint64_t n_msgs, gs_text_fn on_text, void* const* users,
+                                            uint64_t chunk_bytes) {
+  if (!ctxs || !nctx || !comm || (!sched && n_msgs)) return GS_EINVAL;
+  for (uint32_t i = 0; i < nctx; i++)
+    if (!ctxs[i]) return GS_EINVAL;
+  if (!on_text) {
+    ctxs[0]->last_error = "gs_run_partitioned_log: on_text is NULL";
+    return GS_EINVAL;
+  }
+  if (nctx > 64) return GS_EINVAL;  // (a communicator has at most 64 parts)
+  gs_result_sink sinks[64] = {};
+  for (uint32_t i = 0; i < nctx; i++) {
+    sinks[i].want = GS_WANT_LAT_MS;
+    sinks[i].on_lat = text_sink_unused;
+    ctxs[i]->text.fn = on_text;
+    ctxs[i]->text.user = users ? users[i] : nullptr;
+    ctxs[i]->text.chunk = chunk_bytes;
+    ctxs[i]->text.sched = sched;
+  }
+  const gs_status st = run_partitioned(ctxs, nctx, comm, sched, n_msgs, sinks);
+  for (uint32_t i = 0; i < nctx; i++) ctxs[i]->text = Ctx::TextRun{};
+  return st;
 }

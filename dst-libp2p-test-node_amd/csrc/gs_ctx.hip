@@ -280,7 +280,8 @@ extern "C" gs_status gs_run_log(gs_ctx* ctx, const gs_publish* sched, uint64_t n
   if (!on_text) ctx->fail(GS_EINVAL, "gs_run_log: on_text is NULL");
   if (!ctx->mesh_built) ctx->fail(GS_ESTATE, "gs_mesh_converge first");
   if (!sched && n_msgs) ctx->fail(GS_EINVAL, "null schedule");
-  if (ctx->part_parts > 1) ctx->fail(GS_EUNSUPPORTED, "gs_run_log: not on a partitioned context");
+  if (ctx->part_parts > 1) ctx->fail(GS_EUNSUPPORTED, "gs_run_log: not on a partitioned context (gs_run_partitioned_log formats each part's "
+                                                    "own peers)");
   GS_HIP(hipSetDevice(ctx->cfg.device));
   TextCall call(ctx, sched, on_text, user, chunk_bytes);
   gs_result_sink sink{};

@@ -44,7 +44,10 @@ inline long env_int(const char* name, long dflt) {
 // ERR_LIST: a list pull candidate list overflowed; ERR_RING: a list pull candidate
 // fell outside the K-window ring the host bound promised. Both re-run the batch on k_pull.
 // ERR_LAT16: a logged latency of 65535 ms or more for the u16 stream (GS_WANT_LAT_MS).
-enum : uint32_t { ERR_TIME = 1, ERR_HOPS = 2, ERR_MESH = 4, ERR_DEG = 8, ERR_LIST = 16, ERR_RING = 32, ERR_LAT16 = 64 };
+// ERR_LINES: a peer's line counter of the arrival log's text would pass 2^32 - 1 in the batch (k_lt_room).
+enum : uint32_t {
+  ERR_TIME = 1, ERR_HOPS = 2, ERR_MESH = 4, ERR_DEG = 8, ERR_LIST = 16, ERR_RING = 32, ERR_LAT16 = 64, ERR_LINES = 128
+};
 
 // Device buffer owned by a context.
 template <class T>
@@ -220,7 +223,9 @@ struct Ctx {
     uint64_t chunk = 0;
     const gs_publish* sched = nullptr;
   } text;
+  // (N below: the context's own peers, all of them or a part's range [part_u0, part_u0 + part_un))
   DevBuf<uint32_t> d_tcnt;   // [N]
+  uint32_t tcnt_n = 0;       // the rows d_tcnt counts (0: zeroed at the next use, part_set after a new split)
   DevBuf<uint32_t> d_tln;    // [chunk msgs][N]
   DevBuf<uint32_t> d_tgsum;  // [chunk msgs][(N + 63) / 64]
   DevBuf<uint64_t> d_tgoff;
@@ -234,6 +239,11 @@ struct Ctx {
              text_done_ev[2] = {nullptr, nullptr};
   uint32_t text_par = 0;
   bool text_busy = false;
+  // gs_run_partitioned's latencies (part_lat_stage): d_lat_t holds the batch's message-major
+  // latencies and the error word is on its way to h_pinned[30] (deliver skips both steps)
+  bool lat_staged = false;
+  DevBuf<uint64_t> d_lr_tpub;  // [B] a message-sharded batch's publish times and publishers (k_lat_rows)
+  DevBuf<uint32_t> d_lr_pub;
   DevBuf<uint32_t> d_tables; // lat[S*S] | ser_up[S] | ser_dn[S] (u32 ns)
   DevBuf<uint64_t> d_ctrl;   // [4] triple-buffered next-min keys + spare
   // owner-computes pull path (gs_pull_kernel.h)
@@ -389,8 +399,13 @@ void part_dev_bucket(Ctx& c, uint32_t parts);
 void part_dev_scan_count(Ctx& c, uint32_t parts);
 void part_dev_export(Ctx& c, uint32_t parts, gs_part_record* out);
 void part_dev_relax_next(Ctx& c, const gs_part_record* in, uint64_t n);
-bool part_dev_complete(Ctx& c, bool hist, bool store = true);
+bool part_dev_complete(Ctx& c, bool hist, bool store = true, bool lat = false);
 void part_dev_finish(Ctx& c, const gs_result_sink* sink, uint64_t row0);
+// the u16 latencies of a partitioned batch (gs_relax.hip): message-major into d_lat_t with the
+// error word on its way to the host (enqueued), the word once it is there, the hand-over
+void part_lat_stage(Ctx& c, uint32_t B, const gs_publish* ms_sched);
+uint64_t part_lat_err(Ctx& c);
+void part_lat_deliver_ms(Ctx& c, uint32_t B, const gs_result_sink* sink, uint64_t row0);
 void part_abort(Ctx& c);
 bool part_needs_ms(Ctx& c, const gs_publish* sched, uint64_t n_msgs);
 // the list pass over partitioned rows (gs_part.h)

@@ -5,11 +5,16 @@
 // text buffers and two pinned host buffers, the copy of chunk k on the copy
 // stream beside the formatting of chunk k + 1. Included by gs_relax.hip.
 //
+// The context's rows are the peers [u0, u0 + N): all of them (gs_run_log, gs_format_lat_log:
+// u0 = 0), or the range a part of gs_run_partitioned_log owns. Latencies, line numbers and
+// counters are indexed by row; the line carries the global id u0 + row.
+//
 // A line: shadow.data/hosts/peer<u>/main.1000.stdout:<line>:<id> milliseconds: <ms>\n
 //   <id> = the message's preformatted id string (t_pub_ns as %lld; nim: msgId),
 //   <line> = the peer's line counter (u32 [N], carried across batches and calls).
-// Per chunk of nm messages, G = ceil(N / 64) groups of 64 consecutive peers each:
-//   k_lt_count  lane = peer, loop over the chunk's messages: line numbers (the counter
+// Per chunk of nm messages, G = ceil(N / 64) groups of 64 consecutive rows each (a part's
+// first group starts at its first peer, at no multiple of 64 of the global id):
+//   k_lt_count  lane = row, loop over the chunk's messages: line numbers (the counter
 //               carried in a register, stored back once), line lengths, and per
 //               (message, group) the bytes and lines of its 64 peers;
 //   k_lt_scan   one block: exclusive prefix sum of those in (message, group) order
@@ -40,7 +45,8 @@ struct LtArgs {
   uint64_t* goff;         // [nm][G] byte offset of a group's run
   uint64_t* meta;         // [0] bytes, [1] lines, [2] a line counter passed 2^32 - 1
   char* text;
-  uint32_t N, nm, G;
+  uint32_t N, nm, G;      // N: own rows
+  uint32_t u0;            // the peer of row 0
 };
 
 __device__ __forceinline__ uint32_t lt_div10(uint32_t v) { return __umulhi(v, 0xCCCCCCCDu) >> 3; }
@@ -77,12 +83,25 @@ __global__ __launch_bounds__(LT_WAVES * 64) void k_lt_count(LtArgs a) {
       c++;
     }
     if (in) a.ln[(size_t)m * a.N + u] = lg ? c : 0u;
-    uint32_t s = lg ? (lt_len(u, c, idlen, v) | 1u << 16) : 0u;  // <= 64 * 100 bytes, 64 lines
+    uint32_t s = lg ? (lt_len(a.u0 + u, c, idlen, v) | 1u << 16) : 0u;  // <= 64 * 100 bytes, 64 lines
     for (int d = 32; d; d >>= 1) s += __shfl_xor(s, d);
     if (lane == 0) a.gsum[(size_t)m * a.G + g] = s;
   }
   if (in) a.cnt[u] = c;
   if (over) a.meta[2] = 1;
+}
+
+// A whole batch before any of its text leaves (gs_run_partitioned_log: no part hands out a
+// chunk of a batch that fails in any part): would a row's counter pass 2^32 - 1 over the
+// batch's B messages? lane = row; ERR_LINES into the counters' error word.
+__global__ __launch_bounds__(LT_WAVES * 64) void k_lt_room(const uint16_t* __restrict__ lat_t,
+                                                           const uint32_t* __restrict__ cnt, uint32_t N, uint32_t B,
+                                                           uint64_t* counters) {
+  const uint32_t u = blockIdx.x * (LT_WAVES * 64) + threadIdx.x;
+  if (u >= N) return;
+  uint64_t c = cnt[u];
+  for (uint32_t m = 0; m < B; m++) c += lat_t[(size_t)m * N + u] != GS_LAT_NONE;
+  if (c > 0xFFFFFFFFull) atomicOr((unsigned*)&counters[C_ERR], ERR_LINES);
 }
 
 __global__ __launch_bounds__(LT_SCAN_T) void k_lt_scan(LtArgs a) {
@@ -130,7 +149,8 @@ __global__ __launch_bounds__(LT_WAVES * 64) void k_lt_emit(LtArgs a) {
   const uint32_t v = in ? a.lat_t[(size_t)m * a.N + u] : GS_LAT_NONE;
   const bool lg = v != GS_LAT_NONE;
   const uint32_t line = lg ? a.ln[(size_t)m * a.N + u] : 0u;
-  const uint32_t du = lt_digits(u), dl = lt_digits(line), dv = lt_digits(v);
+  const uint32_t id_u = a.u0 + u;  // the peer the line names
+  const uint32_t du = lt_digits(id_u), dl = lt_digits(line), dv = lt_digits(v);
   const uint32_t len = lg ? LT_FIXED + du + dl + idlen + dv : 0u;
   uint32_t inc = len;  // inclusive prefix sum over the lanes
   for (int d = 1; d < 64; d <<= 1) {
@@ -146,7 +166,7 @@ __global__ __launch_bounds__(LT_WAVES * 64) void k_lt_emit(LtArgs a) {
     constexpr char PFX[] = "shadow.data/hosts/peer", MID[] = "/main.1000.stdout:", MSW[] = " milliseconds: ";
 #pragma unroll
     for (int i = 0; i < 22; i++) p[i] = (unsigned char)PFX[i];
-    p = lt_put(p + 22, u, du);
+    p = lt_put(p + 22, id_u, du);
 #pragma unroll
     for (int i = 0; i < 18; i++) p[i] = (unsigned char)MID[i];
     p = lt_put(p + 18, line, dl);
@@ -185,18 +205,23 @@ static uint32_t lt_msg_id(const gs_config& cfg, const gs_publish& p, uint8_t* ou
   return (uint32_t)n;
 }
 
-static void lt_counters(Ctx& c) {  // zero at gs_create (allocated at the first use)
-  if (c.d_tcnt.p) return;
-  c.d_tcnt.alloc(c.cfg.peers);
-  GS_HIP(hipMemsetAsync(c.d_tcnt.p, 0, (size_t)c.cfg.peers * 4, c.stream));
+// The line counters of the context's un rows: zero at gs_create (allocated at the first use),
+// and again when the rows are another range than the counters were kept for (part_set
+// forgets them when the partition changes).
+static void lt_counters(Ctx& c, uint32_t un) {
+  if (c.d_tcnt.p && c.tcnt_n == un) return;
+  c.d_tcnt.alloc(un);
+  GS_HIP(hipMemsetAsync(c.d_tcnt.p, 0, (size_t)un * 4, c.stream));
+  c.tcnt_n = un;
 }
 
 // The text of messages [0, B) (schedule rows sched[0 .. B), message-major latencies
-// lat_t[B][N] on the device, ready on the context's stream) to c.text's callback,
-// first_msg counted from row0.
-static void text_emit(Ctx& c, const uint16_t* lat_t, uint32_t B, const gs_publish* sched, uint64_t row0) {
+// lat_t[B][un] of the peers [u0, u0 + un) on the device, ready on the context's stream)
+// to c.text's callback, first_msg counted from row0.
+static void text_emit(Ctx& c, const uint16_t* lat_t, uint32_t B, const gs_publish* sched, uint64_t row0, uint32_t u0,
+                      uint32_t un) {
   hipStream_t s = c.stream;
-  const uint32_t N = c.cfg.peers, G = (N + 63) / 64;
+  const uint32_t N = un, G = (N + 63) / 64;
   if (!c.copy) GS_HIP(hipStreamCreateWithFlags(&c.copy, hipStreamNonBlocking));
   if (c.text_busy) {  // a call that failed half way: nothing of it is in flight any more
     GS_HIP(hipStreamSynchronize(c.copy));
@@ -209,11 +234,11 @@ static void text_emit(Ctx& c, const uint16_t* lat_t, uint32_t B, const gs_publis
     if (!c.text_done_ev[k]) GS_HIP(hipEventCreateWithFlags(&c.text_done_ev[k], hipEventDisableTiming));
   }
   if (!c.h_tmeta) GS_HIP(hipHostMalloc((void**)&c.h_tmeta, 2 * 4 * 8, hipHostMallocDefault));
-  lt_counters(c);
+  lt_counters(c, un);
   // ids, and every message's bound: N lines of the longest it can have
   std::vector<uint8_t> ids((size_t)B * LT_ID_STRIDE);
   std::vector<uint64_t> bound(B);
-  const uint32_t dpeer = (uint32_t)std::to_string(N - 1).size();
+  const uint32_t dpeer = (uint32_t)std::to_string(u0 + un - 1).size();
   uint64_t bmax = 0, btot = 0;
   for (uint32_t m = 0; m < B; m++) {
     const uint32_t idlen = lt_msg_id(c.cfg, sched[m], &ids[(size_t)m * LT_ID_STRIDE]);
@@ -260,7 +285,7 @@ static void text_emit(Ctx& c, const uint16_t* lat_t, uint32_t B, const gs_publis
     LtArgs a{};
     a.lat_t = lat_t + (size_t)m0 * N; a.ids = c.d_tids.p + (size_t)m0 * LT_ID_STRIDE; a.cnt = c.d_tcnt.p;
     a.ln = c.d_tln.p; a.gsum = c.d_tgsum.p; a.goff = c.d_tgoff.p; a.meta = c.d_tmeta.p; a.text = c.d_text[par].p;
-    a.N = N; a.nm = nm; a.G = G;
+    a.N = N; a.nm = nm; a.G = G; a.u0 = u0;
     GS_HIP(hipMemsetAsync(c.d_tmeta.p, 0, 4 * 8, s));
     k_lt_count<<<(G + LT_WAVES - 1) / LT_WAVES, LT_WAVES * 64, 0, s>>>(a);
     k_lt_scan<<<1, LT_SCAN_T, 0, s>>>(a);
@@ -293,10 +318,16 @@ static void text_emit(Ctx& c, const uint16_t* lat_t, uint32_t B, const gs_publis
   c.text_busy = false;
 }
 
-// gs_run_log's sink (deliver): the finished batch's peer-major d_lat as text.
+// gs_run_log's and gs_run_partitioned_log's sink (deliver): the finished batch's peer-major
+// d_lat of the peers [u0, u0 + un) as text. A partitioned batch comes staged (part_lat_stage:
+// message-major already, every part's error word checked by the caller).
 static void deliver_text(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, uint64_t sink_row0) {
   hipStream_t s = c.stream;
-  if (u0 || un != c.cfg.peers) c.fail(GS_EUNSUPPORTED, "arrival log text: whole peer rows only");
+  if (c.lat_staged) {
+    c.lat_staged = false;
+    text_emit(c, c.d_lat_t.p, b.B, c.text.sched + sink_row0, sink_row0, u0, un);
+    return;
+  }
   c.d_lat_t.alloc((size_t)un * c.cfg.batch);
   dim3 tg((un + 63) / 64, (b.B + 63) / 64);
   k_transpose16<<<tg, TB, 0, s>>>(c.d_lat.p, c.d_lat_t.p, un, b.B);
@@ -305,7 +336,7 @@ static void deliver_text(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, uint6
   GS_HIP(hipStreamSynchronize(s));
   if (c.h_pinned[0] & ERR_LAT16)  // before any text of the batch is handed out
     c.fail(GS_ERANGE, "a logged latency of 65535 ms or more does not fit the arrival log's u16 latencies");
-  text_emit(c, c.d_lat_t.p, b.B, c.text.sched + sink_row0, sink_row0);
+  text_emit(c, c.d_lat_t.p, b.B, c.text.sched + sink_row0, sink_row0, u0, un);
 }
 
 // gs_format_lat_log: the same over a caller's message-major lat_ms[n_msgs][N].
@@ -316,12 +347,12 @@ void format_lat_log(Ctx& c, const gs_publish* sched, uint64_t n_msgs, const uint
   for (uint64_t m0 = 0; m0 < n_msgs; m0 += piece) {
     const uint32_t B = (uint32_t)std::min<uint64_t>(piece, n_msgs - m0);
     GS_HIP(hipMemcpyAsync(c.d_lat_t.p, lat_ms + m0 * N, (size_t)B * N * 2, hipMemcpyHostToDevice, c.stream));
-    text_emit(c, c.d_lat_t.p, B, sched + m0, m0);
+    text_emit(c, c.d_lat_t.p, B, sched + m0, m0, 0, N);
   }
 }
 
 void log_text_reset(Ctx& c) {
-  if (!c.d_tcnt.p) return;
-  GS_HIP(hipMemsetAsync(c.d_tcnt.p, 0, (size_t)c.cfg.peers * 4, c.stream));
+  if (!c.d_tcnt.p || !c.tcnt_n) return;
+  GS_HIP(hipMemsetAsync(c.d_tcnt.p, 0, (size_t)c.tcnt_n * 4, c.stream));
   GS_HIP(hipStreamSynchronize(c.stream));
 }

@@ -311,6 +311,26 @@ __global__ void k_pnext(uint64_t* ctrl, const uint64_t* pcnt) {
   if (threadIdx.x == 0) ctrl[0] = ctrl[1] < pcnt[2] ? ctrl[1] : pcnt[2];
 }
 
+// The logged latencies of a message-sharded batch (gs_comm.hip run_batch_ms): after the
+// all-to-all a part holds its own peers' completion times message-major, tc_t[B][un]; the
+// log line's ms of each (k_complete's rule: nothing where undelivered, nothing for the
+// publisher's own row unless self_log) into lat_t[B][un]. Lane = row, blockIdx.y = message.
+__global__ __launch_bounds__(TB) void k_lat_rows(const uint64_t* __restrict__ tc_t, const uint64_t* __restrict__ tpub,
+                                                 const uint32_t* __restrict__ pub, uint16_t* __restrict__ lat_t,
+                                                 uint32_t un, uint32_t u0, uint32_t self_log, uint64_t* counters) {
+  const uint32_t r = blockIdx.x * TB + threadIdx.x, m = blockIdx.y;
+  if (r >= un) return;
+  const size_t i = (size_t)m * un + r;
+  const uint64_t t = tc_t[i];
+  uint32_t v = GS_LAT_NONE;
+  if (t != INF64 && (self_log || u0 + r != pub[m])) {
+    const uint64_t ms = (t - tpub[m]) / 1000000ull;
+    if (ms >= 0xFFFF) atomicOr((unsigned*)&counters[C_ERR], ERR_LAT16);
+    v = ms < 0xFFFF ? (uint32_t)ms : 0xFFFEu;
+  }
+  lat_t[i] = (uint16_t)v;
+}
+
 template <int FP>
 void part_export_fp(const RelaxArgs& a, unsigned grid, hipStream_t s, gs_part_record* rec, uint64_t cap,
                     uint64_t* pcnt) {
@@ -344,6 +364,7 @@ void part_set(Ctx& c, uint32_t parts, uint32_t part) {
   const uint32_t N = c.cfg.peers;
   if (c.part_open) c.fail(GS_ESTATE, "a partitioned batch is in flight (gs_part_finish first)");
   if (parts < 1 || part >= parts || parts > N) c.fail(GS_EINVAL, "need 1 <= parts <= peers and part < parts");
+  if (parts != c.part_parts || part != c.part_idx) c.tcnt_n = 0;  // the log text's line counters start over
   c.part_parts = parts;
   c.part_idx = part;
   const PartLayout lay{parts, N, 0};
@@ -565,9 +586,9 @@ void part_dev_relax_next(Ctx& c, const gs_part_record* in, uint64_t n) {
 // Completion in two steps, so that several contexts' completions overlap:
 // enqueue the reductions (and the message statistics' copy into pinned memory),
 // then wait and check the gossip proof.
-static void part_dev_complete_enqueue(Ctx& c, bool hist, bool store) {
+static void part_dev_complete_enqueue(Ctx& c, bool hist, bool store, bool lat) {
   const Batch& b = c.part_b;
-  run_complete(c, b, c.part_u0, c.part_un, true, hist, store);
+  run_complete(c, b, c.part_u0, c.part_un, true, hist, store, lat);
   if (!c.cfg.lazy_gossip) return;
   const size_t msb = (size_t)b.B * MS_COLS * 8;
   if (c.h_slms_bytes < msb) {
@@ -605,8 +626,8 @@ static bool part_dev_complete_check(Ctx& c) {
   return ok;
 }
 
-bool part_dev_complete(Ctx& c, bool hist, bool store) {
-  part_dev_complete_enqueue(c, hist, store);
+bool part_dev_complete(Ctx& c, bool hist, bool store, bool lat) {
+  part_dev_complete_enqueue(c, hist, store, lat);
   return part_dev_complete_check(c);
 }
 
@@ -623,14 +644,71 @@ void part_dev_finish(Ctx& c, const gs_result_sink* sink, uint64_t row0) {
   collect_stats(c);
 }
 
-void part_abort(Ctx& c) { c.part_open = false; }
+void part_abort(Ctx& c) {
+  c.part_open = false;
+  c.lat_staged = false;
+}
+
+// The u16 latencies of a partitioned batch, in steps, so that the caller (gs_comm.hip) has
+// every part's error word before any part hands out a line or a block of the batch.
+// part_lat_stage, enqueued: d_lat_t[B][un] message-major — transposed from the completion's
+// peer-major d_lat, or for a message-sharded batch (ms_sched: its B schedule rows) from the
+// exchanged d_tc_t by k_lat_rows — then, when the latencies leave as text, the line counters'
+// room for the batch (k_lt_room), and the error word on its way into h_pinned[30].
+void part_lat_stage(Ctx& c, uint32_t B, const gs_publish* ms_sched) {
+  hipStream_t s = c.stream;
+  const uint32_t un = c.part_un;
+  c.d_lat_t.alloc((size_t)un * std::max(c.cfg.batch, B));
+  if (ms_sched) {
+    std::vector<uint64_t> tp(B);
+    std::vector<uint32_t> pb(B);
+    for (uint32_t m = 0; m < B; m++) {
+      tp[m] = ms_sched[m].t_pub_ns;
+      pb[m] = ms_sched[m].publisher;
+    }
+    c.d_lr_tpub.alloc(std::max(c.cfg.batch, B));
+    c.d_lr_pub.alloc(std::max(c.cfg.batch, B));
+    GS_HIP(hipMemcpyAsync(c.d_lr_tpub.p, tp.data(), (size_t)B * 8, hipMemcpyHostToDevice, s));
+    GS_HIP(hipMemcpyAsync(c.d_lr_pub.p, pb.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+    GS_HIP(hipMemsetAsync(c.d_counters.p + C_ERR, 0, 8, s));  // (the part's own run of its messages checked its word)
+    k_lat_rows<<<dim3((un + TB - 1) / TB, B), TB, 0, s>>>(c.d_tc_t.p, c.d_lr_tpub.p, c.d_lr_pub.p, c.d_lat_t.p, un,
+                                                          c.part_u0, c.cfg.self_log, c.d_counters.p);
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipStreamSynchronize(s));  // (tp / pb leave scope)
+  } else {
+    dim3 tg((un + 63) / 64, (B + 63) / 64);
+    k_transpose16<<<tg, TB, 0, s>>>(c.d_lat.p, c.d_lat_t.p, un, B);
+    GS_HIP(hipGetLastError());
+  }
+  if (c.text.fn) {
+    lt_counters(c, un);
+    k_lt_room<<<(un + LT_WAVES * 64 - 1) / (LT_WAVES * 64), LT_WAVES * 64, 0, s>>>(c.d_lat_t.p, c.d_tcnt.p, un, B,
+                                                                                   c.d_counters.p);
+    GS_HIP(hipGetLastError());
+  }
+  GS_HIP(hipMemcpyAsync(c.h_pinned + 30, c.d_counters.p + C_ERR, 8, hipMemcpyDeviceToHost, s));
+  c.lat_staged = true;
+}
+
+uint64_t part_lat_err(Ctx& c) {
+  GS_HIP(hipStreamSynchronize(c.stream));
+  return c.h_pinned[30] & (ERR_LAT16 | ERR_LINES);
+}
+
+// A staged message-sharded batch into the sink: its text, or the rows / on_lat blocks.
+void part_lat_deliver_ms(Ctx& c, uint32_t B, const gs_result_sink* sink, uint64_t row0) {
+  c.lat_staged = false;
+  if (c.text.fn) text_emit(c, c.d_lat_t.p, B, c.text.sched + row0, row0, c.part_u0, c.part_un);
+  else deliver_rows(c, B, c.part_un, sink, row0);
+}
 
 void part_finish(Ctx& c, const gs_result_sink* sink) {
   if (!c.part_open) c.fail(GS_ESTATE, "gs_part_begin first");
   c.part_open = false;
   const Batch& b = c.part_b;
   const bool gossip = c.cfg.lazy_gossip != 0;
-  run_complete(c, b, c.part_u0, c.part_un, gossip || (sink && sink->summary), sink && sink->summary);
+  run_complete(c, b, c.part_u0, c.part_un, gossip || (sink && sink->summary), sink && sink->summary, true,
+               sink && sink->on_lat);
   if (gossip) {
     std::vector<uint64_t> ms((size_t)b.B * MS_COLS), rel0(b.B);
     GS_HIP(hipMemcpyAsync(ms.data(), c.d_mstat.p, ms.size() * 8, hipMemcpyDeviceToHost, c.stream));
@@ -930,9 +1008,10 @@ void part_lp_route_fix(Ctx& c, uint32_t P, uint32_t me, const uint64_t* base) {
   GS_HIP(hipGetLastError());
 }
 
-// As gs_run's list pass: completion reads the final logs (k_lcomplete) unless
-// the sink takes rows or a summary, or the rows hold fragment groups (k_lfinal
-// -> dense rows -> k_complete).
+// As gs_run's list pass: completion reads the final logs (k_lcomplete, which
+// also writes the logged latencies a sink's on_lat or the log's text take)
+// unless the sink takes rows or a summary, or the rows hold fragment groups
+// (k_lfinal -> dense rows -> k_complete).
 void part_lp_end_enqueue(Ctx& c, const gs_result_sink* sink) {
   const SinkWants w = sink_wants(sink);
   const bool dense = w.rows() || w.summary || c.part_b.FP > 1 || getenv("GS_LPULL_DENSE");
@@ -945,7 +1024,7 @@ void part_lp_end_enqueue(Ctx& c, const gs_result_sink* sink) {
   }
   c.stats.list_pull_batches++;
   c.part_lp = false;
-  part_dev_complete_enqueue(c, w.summary, dense);
+  part_dev_complete_enqueue(c, w.summary, dense, w.lat);
 }
 
 bool part_lp_end_check(Ctx& c) { return part_dev_complete_check(c); }

@@ -834,7 +834,9 @@ static void deliver(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, const gs_r
     k_transpose<<<tg, TB, 0, s>>>(c.d_tc.p, c.d_hops.p, c.d_tc_t.p, c.d_hops_t.p, un, b.B);
     GS_HIP(hipGetLastError());
   }
-  if (w.lat) {
+  if (w.lat && c.lat_staged) {  // a partitioned batch: transposed and checked over every part already
+    c.lat_staged = false;
+  } else if (w.lat) {
     c.d_lat_t.alloc((size_t)un * c.cfg.batch);
     dim3 tg((un + 63) / 64, (b.B + 63) / 64);
     k_transpose16<<<tg, TB, 0, s>>>(c.d_lat.p, c.d_lat_t.p, un, b.B);

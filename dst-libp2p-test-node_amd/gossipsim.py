@@ -158,6 +158,8 @@ SIGNATURES = {
     "gs_comm_check": (i32, [ctypes.c_void_p]),
     "gs_comm_destroy": (i32, [ctypes.c_void_p]),
     "gs_run_partitioned": (i32, [P(ctypes.c_void_p), u32, ctypes.c_void_p, P(GsPublish), u64, P(GsResultSink)]),
+    "gs_run_partitioned_log": (i32, [P(ctypes.c_void_p), u32, ctypes.c_void_p, P(GsPublish), u64, TEXT_FN,
+                                     P(ctypes.c_void_p), u64]),
 }
 COMM_ID_BYTES = 128
 GS_EINVAL = -1
@@ -787,30 +789,99 @@ class Comm:
             raise GossipSimError(rc, "gs_comm_get_id failed (RCCL not loadable?)")
         return buf.raw
 
-    def run_partitioned(self, sims, schedule, collect=True):
+    def run_partitioned(self, sims, schedule, collect=True, summary=False, on_lat=None, block_msgs=0, want=None):
         """gs_run_partitioned over this process's Simulators (local: one per part,
         in part order; RCCL: this rank's). -> per part {"t_complete", "hops",
-        "peer_range"} [M, own peers] (collect) or None."""
+        "peer_range"} [M, own peers] (collect) or None.
+        on_lat(part, first_msg, lat_ms[n, own peers] uint16): every part's logged
+        latency stream (GS_WANT_LAT_MS) in blocks of block_msgs messages, alone
+        (collect=False) or beside the arrays; the parts' blocks side by side are
+        Simulator.run's on_lat stream. summary: also "summary" per part (the
+        gs_msg_summary rows as a ctypes array). want: the sinks' want word, when
+        it is not to follow from on_lat (tests of the sink rules)."""
         schedule = sims[0]._schedule(schedule)
         M = len(schedule)
         arr = (ctypes.c_void_p * len(sims))(*[s.ctx for s in sims])
         sinks, keep, out = (GsResultSink * len(sims))(), [], []
+        err = []
         for i, sim in enumerate(sims):
             part = i if self.local else self.rank
             u0, u1 = part * sim.peers // self.parts, (part + 1) * sim.peers // self.parts
             sim.part_range = (u0, u1)
+            if on_lat is not None:
+                def _lcb(user, first, n, peers, lat, part=part):
+                    try:
+                        on_lat(part, int(first), np.ctypeslib.as_array(lat, (n, peers)))
+                    except BaseException as e:  # (no exception crosses the C frames)
+                        err.append(e)
+
+                lcb = LAT_FN(_lcb)
+                keep.append(lcb)
+                sinks[i].on_lat = lcb
+                sinks[i].block_msgs = block_msgs
+                sinks[i].want = WANT_LAT_MS
+            if want is not None:
+                sinks[i].want = want
+            res = {"peer_range": (u0, u1)}
+            out.append(res)
+            if summary:
+                sm = (GsMsgSummary * M)()
+                sinks[i].summary = ctypes.cast(sm, P(GsMsgSummary))
+                res["summary"] = sm
             if collect:
                 tc = np.zeros(M * (u1 - u0), np.uint64)
                 hp = np.zeros(M * (u1 - u0), np.uint8)
                 keep += [tc, hp]
                 sinks[i].t_complete_ns = _ptr(tc, u64)
                 sinks[i].hops = _ptr(hp, u8)
-                out.append({"t_complete": tc.reshape(M, u1 - u0), "hops": hp.reshape(M, u1 - u0),
-                            "peer_range": (u0, u1)})
-        rc = lib().gs_run_partitioned(arr, len(sims), self.h, schedule, M, sinks if collect else None)
+                res.update(t_complete=tc.reshape(M, u1 - u0), hops=hp.reshape(M, u1 - u0))
+        use_sinks = collect or summary or on_lat is not None or want is not None
+        rc = lib().gs_run_partitioned(arr, len(sims), self.h, schedule, M, sinks if use_sinks else None)
         if rc:
             raise GossipSimError(rc, lib().gs_last_error(sims[0].ctx).decode())
-        return out if collect else None
+        if err:
+            raise err[0]
+        return out if collect or summary else None
+
+    def run_partitioned_log(self, sims, schedule, on_text=None, paths=None, chunk_bytes=0):
+        """gs_run_partitioned_log: run_partitioned whose only output is the arrival log's
+        text, each part formatting its own peers' lines on its device: written to
+        paths[i] (one file per part), and / or handed to
+        on_text(part, first_msg, n_msgs, text_bytes, lines) chunk by chunk. A part's
+        chunks in order are Simulator.run_log's text with only that part's peers' lines
+        kept. With neither, the library gets NULL and refuses. -> lines per part."""
+        schedule = sims[0]._schedule(schedule)
+        arr = (ctypes.c_void_p * len(sims))(*[s.ctx for s in sims])
+        parts = [i if self.local else self.rank for i in range(len(sims))]
+        for sim, part in zip(sims, parts):
+            sim.part_range = (part * sim.peers // self.parts, (part + 1) * sim.peers // self.parts)
+        users = (ctypes.c_void_p * len(sims))(*range(len(sims)))  # user = the context's index
+        files = [open(p, "wb", buffering=0) for p in paths] if paths is not None else None
+        total, err = [0] * len(sims), []
+
+        def _tcb(user, first, n, text, nbytes, lines):
+            i = int(user or 0)
+            total[i] += lines
+            try:
+                buf = (ctypes.c_char * nbytes).from_address(text) if nbytes else b""
+                if files is not None:
+                    files[i].write(buf)
+                if on_text is not None:
+                    on_text(parts[i], int(first), int(n), bytes(buf), int(lines))
+            except BaseException as e:  # (no exception crosses the C frames)
+                err.append(e)
+
+        cb = TEXT_FN(_tcb) if (on_text is not None or files is not None) else TEXT_FN()
+        try:
+            rc = lib().gs_run_partitioned_log(arr, len(sims), self.h, schedule, len(schedule), cb, users, chunk_bytes)
+        finally:
+            for f in files or []:
+                f.close()
+        if rc:
+            raise GossipSimError(rc, lib().gs_last_error(sims[0].ctx).decode())
+        if err:
+            raise err[0]
+        return total
 
     def close(self):
         if self.h:

@@ -168,8 +168,8 @@ enum { GS_WANT_T_COMPLETE = 1u, GS_WANT_HOPS = 2u, GS_WANT_LAT_MS = 4u };
  *    as the selection flags);
  *  - summary: [n_msgs] per-message latency reductions;
  *  - on_lat: the logged latency in ms, u16, streamed in the same blocks; set
- *    iff want has GS_WANT_LAT_MS (ABI 9). gs_run only (gs_run_partitioned
- *    returns GS_EUNSUPPORTED). */
+ *    iff want has GS_WANT_LAT_MS (ABI 9). gs_run_partitioned streams each
+ *    part's own peers: blocks of [n_msgs][own peers]. */
 typedef struct gs_result_sink {
     uint64_t* t_complete_ns;  /* completion time of message m at peer u (GS_UNDELIVERED if never) */
     uint8_t*  hops;           /* hop count of the completing fragment (0 at the publisher)        */
@@ -449,9 +449,12 @@ gs_status gs_format_lat_log(struct gs_ctx*, const gs_publish* sched, uint64_t n_
                             const uint16_t* lat_ms, gs_text_fn on_text, void* user,
                             uint64_t chunk_bytes);
 
-/* Per-peer line counters: zero at gs_create, carried across gs_run_log / gs_format_lat_log
- * calls (as one gs_log carries them across gs_log_write_lat calls); this zeroes them.
- * After a failed call they are unspecified until this call. */
+/* Per-peer line counters: zero at gs_create, carried across gs_run_log / gs_format_lat_log /
+ * gs_run_partitioned_log calls (as one gs_log carries them across gs_log_write_lat calls);
+ * this zeroes them. They are per context and cover the context's own peers — all of them, or
+ * the range of its partition — and are also zeroed when the context's partition
+ * (parts, part) changes (gs_set_partition, gs_run_partitioned with another communicator
+ * size). After a failed call they are unspecified until this call. */
 gs_status gs_log_text_reset(struct gs_ctx*);
 
 /* Host-only: the longest line cfg can produce, in bytes (sizes the buffers). */
@@ -570,9 +573,31 @@ gs_status gs_comm_destroy(gs_comm* comm);
  * the batch's messages for all peers, one all-to-all hands every part its own
  * peers' rows; gs_stats.ms_batches counts them). Collective over the
  * communicator. Results are bit-identical to gs_run. GS_EUNSUPPORTED: per-peer
- * traffic (gs_set_traffic), and sink summaries of a message-sharded batch. */
+ * traffic (gs_set_traffic), and sink summaries of a message-sharded batch.
+ * Every sinks[i] follows gs_result_sink's rules (GS_EINVAL otherwise); on_lat
+ * receives [n][own peers] u16, and the parts' blocks side by side are gs_run's
+ * on_lat stream. GS_ERANGE (a logged latency of 65535 ms or more): no part, and
+ * no rank, hands out a block of the failing batch, and every rank returns it. */
 gs_status gs_run_partitioned(struct gs_ctx* const* ctxs, uint32_t nctx, gs_comm* comm, const gs_publish* sched,
                              uint64_t n_msgs, const gs_result_sink* sinks);
+
+/* gs_run_partitioned whose only output is the arrival log's text, each part formatting
+ * the lines of its own peers on its own device. on_text is called with users[i] for
+ * ctxs[i] (users may be NULL: user = NULL for every part).
+ * For the part that owns peers [u0, u1), its calls' text in call order is gs_run_log's text
+ * of an unpartitioned context (same config and schedule, fresh line counters) with only the
+ * lines of peers in [u0, u1) kept, in their order there: message-major, ascending peer id
+ * inside a message. So the parts' lines together are gs_run_log's lines, and a peer's line
+ * numbers do not depend on the split. Per part, first_msg / n_msgs tile the schedule in
+ * order; chunks hold whole messages and never span batches; chunk_bytes is per part (0 =
+ * the default, a smaller value is raised to one message's bound over the part's peers).
+ * All callbacks run on the calling thread; the order of calls between parts is unspecified.
+ * Line counters: see gs_log_text_reset. GS_ERANGE (a latency of 65535 ms or more, a line
+ * counter passing 2^32 - 1): no part, and no rank, hands out text of the failing batch, and
+ * every rank returns it. GS_EINVAL: on_text is NULL. */
+gs_status gs_run_partitioned_log(struct gs_ctx* const* ctxs, uint32_t nctx, gs_comm* comm,
+                                 const gs_publish* sched, uint64_t n_msgs,
+                                 gs_text_fn on_text, void* const* users, uint64_t chunk_bytes);
 
 #ifdef __cplusplus
 }

@@ -150,6 +150,9 @@ extern "C" {
     pub fn gs_comm_destroy(comm: *mut gs_comm) -> gs_status;
     pub fn gs_run_partitioned(ctxs: *const *mut gs_ctx, nctx: u32, comm: *mut gs_comm, sched: *const gs_publish,
                               n_msgs: u64, sinks: *const gs_result_sink) -> gs_status;
+    pub fn gs_run_partitioned_log(ctxs: *const *mut gs_ctx, nctx: u32, comm: *mut gs_comm, sched: *const gs_publish,
+                                  n_msgs: u64, on_text: gs_text_fn, users: *const *mut c_void, chunk_bytes: u64)
+                                  -> gs_status;
     pub fn gs_set_partition(ctx: *mut gs_ctx, parts: u32, part: u32) -> gs_status;
     pub fn gs_part_begin(ctx: *mut gs_ctx, sched: *const gs_publish, n_msgs: u64, out_min_key: *mut u64)
                          -> gs_status;
