@@ -71,7 +71,7 @@ struct DevBuf {
 
 // Counters written by kernels: index constants into Ctx::d_counters.
 constexpr uint32_t H_PINNED_WORDS = 32;
-constexpr uint32_t GLP_QUIET = 8;  // see run_messages run_glp
+constexpr uint32_t GLP_QUIET = 8;  // see glp_account (gs_run.h)
 
 enum : uint32_t {
   C_FD = 0, C_R = 1, C_DELIV = 2, C_LAT_SUM = 3, C_LAT_MAX = 4, C_BUCKETS = 5,
@@ -344,7 +344,7 @@ struct Ctx {
   } ct[2];
   uint32_t ct_par = 0;          // the table set the next batch prepared in line uses
   std::function<void()> pass_poll;  // called by the list pass between groups of passes (the chain ahead)
-  uint64_t run_batch = 0;           // the batch loop's iteration in this run_messages_impl call (GS_LPULL_CAP_BATCHES)
+  uint64_t run_batch = 0;           // the batch loop's iteration in this gs_run call (Run::run, GS_LPULL_CAP_BATCHES)
   hipStream_t pass_ms = nullptr;    // churn runs: the passes' stream off the chain's XCDs (GS_PASS_XCDS)
   hipEvent_t pass_ev[2] = {nullptr, nullptr};
   DevBuf<uint8_t> d_gnz;       // [N] the row's IHAVE plane of the built heartbeat is not empty
@@ -355,6 +355,7 @@ struct Ctx {
   // stats
   gs_stats stats{};
   std::vector<hipEvent_t> ev_pool;
+  size_t ev_n = 0;  // timing: the cursor of the run in progress into ev_pool (gs_relax.hip run_ev)
   int num_cus = 0;
   std::string gossip_why;  // the message that broke the last partitioned gossip no-op proof
 

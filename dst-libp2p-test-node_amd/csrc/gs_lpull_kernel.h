@@ -2398,137 +2398,49 @@ __global__ __launch_bounds__(64) void k_part_combine(PartCtl pc, uint32_t P, uin
   }
 }
 
-void lpull_dispatch_part(uint32_t FP, const LPullArgs& a, unsigned grid, hipStream_t s) {
-  const bool ch8 = lpull_chunks(a.L) == 8;
-#define GS_LPP(F)                                                      \
-  if (ch8) k_lpull<F, 8, false, true><<<grid, TB, 0, s>>>(a);           \
-  else k_lpull<F, 16, false, true><<<grid, TB, 0, s>>>(a);
+// One k_lpull launch under the flag set FL (k_lpull's trailing parameters, in its
+// order: IDW, PART, GOS, CHN, NOLOG; the ones left out are off): the instantiation
+// for the batch's fragment lanes per message (FP) and chunks per row.
+template <int FP, bool... FL>
+void lpull_launch_fp(const LPullArgs& a, unsigned grid, hipStream_t s) {
+  if (lpull_chunks(a.L) == 8) k_lpull<FP, 8, FL...><<<grid, TB, 0, s>>>(a);
+  else k_lpull<FP, 16, FL...><<<grid, TB, 0, s>>>(a);
+}
+template <bool... FL>
+void lpull_launch(uint32_t FP, const LPullArgs& a, unsigned grid, hipStream_t s) {
   switch (FP) {
-    case 1: GS_LPP(1) break;
-    case 2: GS_LPP(2) break;
-    case 4: GS_LPP(4) break;
-    case 8: GS_LPP(8) break;
-    default: GS_LPP(16) break;
+    case 1: return lpull_launch_fp<1, FL...>(a, grid, s);
+    case 2: return lpull_launch_fp<2, FL...>(a, grid, s);
+    case 4: return lpull_launch_fp<4, FL...>(a, grid, s);
+    case 8: return lpull_launch_fp<8, FL...>(a, grid, s);
+    default: return lpull_launch_fp<16, FL...>(a, grid, s);
   }
-#undef GS_LPP
 }
 
-// One pass of a GOS batch: its control, the sender planes when a heartbeat's
-// senders just became final, the pass itself (rows of one fragment).
-// The churn list pass (CHN) by fragment lanes per message and chunks per row.
-template <bool GOS>
-void lpull_dispatch_chn(uint32_t FP, const LPullArgs& a, unsigned grid, hipStream_t s) {
-#define GS_LPC(F)                                                                             \
-  if (lpull_chunks(a.L) == 8) k_lpull<F, 8, false, false, GOS, true><<<grid, TB, 0, s>>>(a);  \
-  else k_lpull<F, 16, false, false, GOS, true><<<grid, TB, 0, s>>>(a)
-  switch (FP) {
-    case 1: GS_LPC(1); break;
-    case 2: GS_LPC(2); break;
-    case 4: GS_LPC(4); break;
-    case 8: GS_LPC(8); break;
-    default: GS_LPC(16); break;
-  }
-#undef GS_LPC
-}
-
-void lpull_dispatch_gos(const LPullArgs& a, unsigned grid, hipStream_t s) {
-  k_lctl<<<1, 64, 0, s>>>(a);
-  const uint32_t FP = a.L / a.B;  // fragment lanes per message (rows of fragment groups: one lane per fragment)
-  if (a.ccol) {  // churn
-    if (lpull_chunks(a.L) == 8) k_gsend<8, true><<<grid, TB, 0, s>>>(a);
-    else k_gsend<16, true><<<grid, TB, 0, s>>>(a);
-    lpull_dispatch_chn<true>(FP, a, grid, s);
-    return;
-  }
-  if (a.idw) {  // IDONTWANT (dense final keys; single lanes or fragment groups)
-    if (lpull_chunks(a.L) == 8) {
-      k_gsend<8><<<grid, TB, 0, s>>>(a);
-      switch (FP) {
-        case 1: k_lpull<1, 8, true, false, true><<<grid, TB, 0, s>>>(a); break;
-        case 2: k_lpull<2, 8, true, false, true><<<grid, TB, 0, s>>>(a); break;
-        case 4: k_lpull<4, 8, true, false, true><<<grid, TB, 0, s>>>(a); break;
-        case 8: k_lpull<8, 8, true, false, true><<<grid, TB, 0, s>>>(a); break;
-        default: k_lpull<16, 8, true, false, true><<<grid, TB, 0, s>>>(a); break;
-      }
+// One pass of a batch on the whole graph (a peer-partitioned batch's pass is
+// lpull_launch<false, true>, gs_part.h). gos (lazy gossip inside the pass): its
+// control, the sender planes when a heartbeat's senders just became final, then
+// the pass itself. The flag sets that exist: churn (a.ccol) or IDONTWANT (a.idw:
+// dense final keys), each with or without gos, rows of single lanes or fragment
+// groups; nolog (the batch keeps no final log: PathPlan::nolog's rule, gs_run.h)
+// for the plain pass of single lanes only.
+void lpull_dispatch(uint32_t FP, const LPullArgs& a, unsigned grid, hipStream_t s, bool gos, bool nolog) {
+  const bool chn = a.ccol != nullptr;
+  if (gos) {
+    k_lctl<<<1, 64, 0, s>>>(a);
+    const bool ch8 = lpull_chunks(a.L) == 8;
+    if (chn) {
+      if (ch8) k_gsend<8, true><<<grid, TB, 0, s>>>(a);
+      else k_gsend<16, true><<<grid, TB, 0, s>>>(a);
     } else {
-      k_gsend<16><<<grid, TB, 0, s>>>(a);
-      switch (FP) {
-        case 1: k_lpull<1, 16, true, false, true><<<grid, TB, 0, s>>>(a); break;
-        case 2: k_lpull<2, 16, true, false, true><<<grid, TB, 0, s>>>(a); break;
-        case 4: k_lpull<4, 16, true, false, true><<<grid, TB, 0, s>>>(a); break;
-        case 8: k_lpull<8, 16, true, false, true><<<grid, TB, 0, s>>>(a); break;
-        default: k_lpull<16, 16, true, false, true><<<grid, TB, 0, s>>>(a); break;
-      }
-    }
-    return;
-  }
-  if (lpull_chunks(a.L) == 8) {
-    k_gsend<8><<<grid, TB, 0, s>>>(a);
-    switch (FP) {
-      case 1: k_lpull<1, 8, false, false, true><<<grid, TB, 0, s>>>(a); break;
-      case 2: k_lpull<2, 8, false, false, true><<<grid, TB, 0, s>>>(a); break;
-      case 4: k_lpull<4, 8, false, false, true><<<grid, TB, 0, s>>>(a); break;
-      case 8: k_lpull<8, 8, false, false, true><<<grid, TB, 0, s>>>(a); break;
-      default: k_lpull<16, 8, false, false, true><<<grid, TB, 0, s>>>(a); break;
-    }
-  } else {
-    k_gsend<16><<<grid, TB, 0, s>>>(a);
-    switch (FP) {
-      case 1: k_lpull<1, 16, false, false, true><<<grid, TB, 0, s>>>(a); break;
-      case 2: k_lpull<2, 16, false, false, true><<<grid, TB, 0, s>>>(a); break;
-      case 4: k_lpull<4, 16, false, false, true><<<grid, TB, 0, s>>>(a); break;
-      case 8: k_lpull<8, 16, false, false, true><<<grid, TB, 0, s>>>(a); break;
-      default: k_lpull<16, 16, false, false, true><<<grid, TB, 0, s>>>(a); break;
+      if (ch8) k_gsend<8><<<grid, TB, 0, s>>>(a);
+      else k_gsend<16><<<grid, TB, 0, s>>>(a);
     }
   }
+  if (nolog) return lpull_launch_fp<1, false, false, false, false, true>(a, grid, s);
+  if (chn) return gos ? lpull_launch<false, false, true, true>(FP, a, grid, s)
+                      : lpull_launch<false, false, false, true>(FP, a, grid, s);
+  if (a.idw) return gos ? lpull_launch<true, false, true>(FP, a, grid, s) : lpull_launch<true>(FP, a, grid, s);
+  return gos ? lpull_launch<false, false, true>(FP, a, grid, s) : lpull_launch<>(FP, a, grid, s);
 }
 
-// nolog: the batch keeps no final log (run_lpull_batch's rule; FP = 1, the plain pass)
-void lpull_dispatch(uint32_t FP, const LPullArgs& a, unsigned grid, hipStream_t s, bool nolog = false) {
-  if (nolog) {
-    if (lpull_chunks(a.L) == 8) k_lpull<1, 8, false, false, false, false, true><<<grid, TB, 0, s>>>(a);
-    else k_lpull<1, 16, false, false, false, false, true><<<grid, TB, 0, s>>>(a);
-    return;
-  }
-  if (a.ccol) {  // churn without lazy gossip (rows of fragment groups: FP lanes per message)
-    lpull_dispatch_chn<false>(FP, a, grid, s);
-    return;
-  }
-  if (a.idw) {  // IDONTWANT (dense final keys; single lanes or fragment groups)
-    if (lpull_chunks(a.L) == 8) {
-      switch (FP) {
-        case 1: k_lpull<1, 8, true><<<grid, TB, 0, s>>>(a); break;
-        case 2: k_lpull<2, 8, true><<<grid, TB, 0, s>>>(a); break;
-        case 4: k_lpull<4, 8, true><<<grid, TB, 0, s>>>(a); break;
-        case 8: k_lpull<8, 8, true><<<grid, TB, 0, s>>>(a); break;
-        default: k_lpull<16, 8, true><<<grid, TB, 0, s>>>(a); break;
-      }
-      return;
-    }
-    switch (FP) {
-      case 1: k_lpull<1, 16, true><<<grid, TB, 0, s>>>(a); break;
-      case 2: k_lpull<2, 16, true><<<grid, TB, 0, s>>>(a); break;
-      case 4: k_lpull<4, 16, true><<<grid, TB, 0, s>>>(a); break;
-      case 8: k_lpull<8, 16, true><<<grid, TB, 0, s>>>(a); break;
-      default: k_lpull<16, 16, true><<<grid, TB, 0, s>>>(a); break;
-    }
-    return;
-  }
-  if (lpull_chunks(a.L) == 8) {
-    switch (FP) {
-      case 1: k_lpull<1, 8><<<grid, TB, 0, s>>>(a); break;
-      case 2: k_lpull<2, 8><<<grid, TB, 0, s>>>(a); break;
-      case 4: k_lpull<4, 8><<<grid, TB, 0, s>>>(a); break;
-      case 8: k_lpull<8, 8><<<grid, TB, 0, s>>>(a); break;
-      default: k_lpull<16, 8><<<grid, TB, 0, s>>>(a); break;
-    }
-    return;
-  }
-  switch (FP) {
-    case 1: k_lpull<1, 16><<<grid, TB, 0, s>>>(a); break;
-    case 2: k_lpull<2, 16><<<grid, TB, 0, s>>>(a); break;
-    case 4: k_lpull<4, 16><<<grid, TB, 0, s>>>(a); break;
-    case 8: k_lpull<8, 16><<<grid, TB, 0, s>>>(a); break;
-    default: k_lpull<16, 16><<<grid, TB, 0, s>>>(a); break;
-  }
-}

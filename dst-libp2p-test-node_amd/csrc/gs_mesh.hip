@@ -1394,7 +1394,7 @@ static void churn_ring_on(Ctx& c, uint64_t h_lo, uint64_t h_hi) {
 
 // The epoch chain of a churn list-pass batch enqueued in slices (the batch
 // after the current one runs its chain beside the current batch's passes,
-// gs_relax.hip ChnAhead): epochs churn_state + 1 .. h1 on stream s, the mask
+// gs_run.h Ahead): epochs churn_state + 1 .. h1 on stream s, the mask
 // ring only (no ELL snapshots, no inverse IHAVE lists: the list pass reads
 // neither), the hook after every epoch (the batch tables' chunks). The ring
 // bookkeeping (churn_state, ring_lo / hi) moves when the last epoch is enqueued.

@@ -820,10 +820,7 @@ bool part_lp_begin(Ctx& c, const gs_publish* sched, uint64_t n_msgs) {
             s>>>(la, c.d_skey.p, c.d_slane.p, c.d_scnt.p);
   k_lpub<<<(b.B * b.Fe + 255) / 256, 256, 0, s>>>(la, b.Fe);
   GS_HIP(hipGetLastError());
-  uint64_t auto_bpc = 4;  // as run_lpull_batch: whole blocks per CU by the rows this part owns
-  while (auto_bpc < 16 && (uint64_t)un >= (uint64_t)c.num_cus * PULL_WAVES * 32 * auto_bpc * 2) auto_bpc *= 2;
-  c.part_lpgrid = (unsigned)std::max<uint64_t>(
-      1, std::min<uint64_t>(((uint64_t)un + PULL_WAVES - 1) / PULL_WAVES, (uint64_t)c.num_cus * auto_bpc));
+  c.part_lpgrid = lpull_grid(un, c.num_cus);  // by the rows this part owns
   // the seeds' min key lands in pinned word 28; part_lp_seed_min waits for it
   // (the caller begins every part first, so that their setups overlap)
   GS_HIP(hipMemcpyAsync(c.h_pinned + 28, c.d_pctrl.p + 2 * 4 + 3, 8, hipMemcpyDeviceToHost, s));
@@ -849,7 +846,7 @@ void part_lp_set(Ctx& c, uint64_t records, uint64_t minp) {
 
 void part_lp_pass(Ctx& c) {
   const LPullArgs la = part_lp_args(c);
-  lpull_dispatch_part(c.part_b.FP, la, c.part_lpgrid, c.stream);
+  lpull_launch<false, true>(c.part_b.FP, la, c.part_lpgrid, c.stream);  // PART
   GS_HIP(hipGetLastError());
   c.part_lppass++;
   c.stats.relax_launches++;

@@ -959,10 +959,31 @@ static void collect_stats(Ctx& c) {
 }
 
 
+// Timing events come from a per-context pool: [0] run start, [1] run end, then
+// one (start, scan end, end) triple around every relaxation launch; c.ev_n is
+// the cursor of the run in progress (Run, gs_run.h).
+static hipEvent_t run_ev(Ctx& c, size_t i) {
+  while (c.ev_pool.size() <= i) {
+    hipEvent_t e;
+    GS_HIP(hipEventCreate(&e));
+    c.ev_pool.push_back(e);
+  }
+  return c.ev_pool[i];
+}
+// One pass of the pull or list path, under timing as (start, mid, end): the whole pass is frontier time.
+template <class Fn>
+static void timed_pass(Ctx& c, hipStream_t s, Fn&& launch) {
+  if (!c.timing) return launch();
+  GS_HIP(hipEventRecord(run_ev(c, c.ev_n), s));
+  GS_HIP(hipEventRecord(run_ev(c, c.ev_n + 1), s));
+  launch();
+  GS_HIP(hipEventRecord(run_ev(c, c.ev_n + 2), s));
+  c.ev_n += 3;
+}
+
 // One batch on the owner-computes path (gs_pull_kernel.h): seed, then passes in
 // chunks of 8 until a pass decides DONE (one host read of the ctrl slots per chunk).
-template <class EvFn>
-static void run_pull_batch(Ctx& c, const Batch& b, EvFn& ev, size_t& n_ev, int dev_cus) {
+static void run_pull_batch(Ctx& c, const Batch& b) {
   const uint32_t N = c.cfg.peers, L = b.L;
   hipStream_t s = c.stream;
   const size_t NL = (size_t)N * L;
@@ -993,20 +1014,12 @@ static void run_pull_batch(Ctx& c, const Batch& b, EvFn& ev, size_t& n_ev, int d
   pa.N = N; pa.B = b.B; pa.L = L; pa.S = c.S; pa.sb = b.sb; pa.tshift = b.tshift;
   // 33 KB of LDS per block: 4 blocks (16 waves, 16 rows in flight) per CU
   const unsigned grid = (unsigned)std::max<uint64_t>(
-      1, std::min<uint64_t>(((uint64_t)N + PULL_WAVES - 1) / PULL_WAVES, (uint64_t)dev_cus * 4));
+      1, std::min<uint64_t>(((uint64_t)N + PULL_WAVES - 1) / PULL_WAVES, (uint64_t)c.num_cus * 4));
   uint32_t pass = 0;
   for (;;) {
     for (uint32_t q = 0; q < 8; q++) {
       pa.pass = pass++;
-      if (c.timing) {  // (start, mid, end): the whole pass is frontier time
-        GS_HIP(hipEventRecord(ev(n_ev), s));
-        GS_HIP(hipEventRecord(ev(n_ev + 1), s));
-        pull_dispatch(b.FP, pa, grid, s);
-        GS_HIP(hipEventRecord(ev(n_ev + 2), s));
-        n_ev += 3;
-      } else {
-        pull_dispatch(b.FP, pa, grid, s);
-      }
+      timed_pass(c, s, [&] { pull_dispatch(b.FP, pa, grid, s); });
     }
     GS_HIP(hipGetLastError());
     GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_pctrl.p, 12 * 8, hipMemcpyDeviceToHost, s));
@@ -1086,13 +1099,7 @@ static uint32_t lpull_ring(Ctx& c, const Batch& b, uint64_t delta, uint32_t* lb,
   return (uint32_t)K;
 }
 
-// One batch on the list pull path: k_seed appends the first sends to a seed
-// list (no dense key table to reset), k_lseed files them into the candidate
-// lists, k_lpub logs the publishers' own lanes, then passes in chunks of 8 as
-// on the k_pull path; completion reads the final logs (k_lcomplete) unless a
-// caller needs dense rows (k_lfinal).
-// Returns false (counters restored) when a list overflowed: the caller re-runs
-// the batch on k_pull.
+// What a batch on the list pull path (run_lpull_batch) can carry.
 // Lazy gossip inside the passes (GOS): the batch's heartbeats relative to
 // every t_pub (lockstep) and the IHAVE travel bounds.
 struct GosRun {
@@ -1106,7 +1113,7 @@ struct ChnRun {
   uint32_t par;  // the table set (Ctx::ct) chn_begin filled for the batch
 };
 
-// Batch slices (run_slices): S batches of the same shape as one pass over S
+// Batch slices (Run::try_slices, gs_run.h): S batches of the same shape as one pass over S
 // copies of the graph, slice j's rows j * N1 + peer; the copies' mesh rows,
 // reverse positions and stages (d_smesh, d_srpos, d_sstage), the publishers
 // as slice rows (spub, k_lpull / k_lpub) and as peers (lpub, k_seed).
@@ -1118,7 +1125,7 @@ struct Slices {
 
 // No-log batch (k_lpull<1, CH, .., NOLOG>): the caller reads only
 // counters, so the passes write no final log and complete the batch themselves.
-// on: asked for by the caller (run_messages_impl's rule). After the batch: inexact = a final
+// on: asked for by the caller (PathPlan::nolog's rule, gs_run.h). After the batch: inexact = a final
 // time reached 2^38 ns, where the passes' 32-bit ms are not k_lsum's (the counters are restored
 // and the caller runs the batch again with its log); else tmax / deliv, the batch's latest
 // final time after t_pub and its deliveries, for the no-op proof of a lockstep batch.
@@ -1128,25 +1135,64 @@ struct NoLog {
 };
 constexpr uint64_t NOLOG_TLIM = 1ull << 38;  // (t >> 6) / 15625 in 32 bits
 
-template <class EvFn>
-static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvFn& ev, size_t& n_ev, int dev_cus,
-                            bool dense, bool idw, const GosRun* gos = nullptr, const ChnRun* chn = nullptr,
-                            const Slices* sl = nullptr, NoLog* nl = nullptr) {
-  const uint32_t N0 = c.cfg.peers, L = b.L;
-  const uint32_t N = sl ? sl->S * N0 : N0;  // the pass's rows
+// What one list-pass batch runs with: dense rows for its reader (k_lfinal), IDONTWANT
+// (dense final keys all along), lazy gossip and churn inside the passes, batch slices,
+// the no-log form.
+struct LpOpts {
+  bool dense = false, idw = false;
+  const GosRun* gos = nullptr;
+  const ChnRun* chn = nullptr;
+  const Slices* sl = nullptr;
+  NoLog* nl = nullptr;
+};
+
+// The list pass's grid for `rows` rows (a part passes the rows it owns).
+// 40 KB of LDS per block: 4 blocks (16 waves, 16 rows in flight) resident per
+// CU. Large graphs launch up to 16 blocks per CU so that a pass's tail is
+// made of short blocks, keeping >= 32 rows per wave (1M peers: 54.3 ms per
+// step at 4 blocks per CU, 53.1 at 16; 100k peers: 7.8 ms at 16, 6.8 at 4;
+// profiles/r02_v7/lpull_grid_sweep.txt)
+// a power of two: 15 per CU measured 56.4 ms against 53.1 at 16 on one box
+static unsigned lpull_grid(uint64_t rows, int cus) {
+  uint64_t bpc = 4;  // whole blocks per CU
+  while (bpc < 16 && rows >= (uint64_t)cus * PULL_WAVES * 32 * bpc * 2) bpc *= 2;
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((rows + PULL_WAVES - 1) / PULL_WAVES, (uint64_t)cus * bpc));
+}
+
+// Test knobs, read per batch: GS_LPULL_CAP's small lists force the overflow re-run;
+// GS_LPULL_CAP_BATCHES (comma-separated 0-based indices of the run's batch loop, in run
+// order: after the class regrouping) keeps the cap to the listed batches
+static uint32_t lpull_cap(const Ctx& c, uint32_t ls) {
+  long cap = env_int("GS_LPULL_CAP", (long)ls);
+  const char* capb = getenv("GS_LPULL_CAP_BATCHES");
+  if (capb && *capb) {
+    bool listed = false;
+    for (const char* q = capb; *q && !listed;) {
+      char* end = nullptr;
+      const unsigned long long v = strtoull(q, &end, 10);
+      listed = end != q && v == c.run_batch;
+      q = end != q ? end : q + 1;
+      while (*q == ',' || *q == ' ') q++;
+    }
+    if (!listed) cap = (long)ls;
+  }
+  return (uint32_t)std::min<long>(std::max(1l, cap), (long)ls);
+}
+
+// The batch's buffers, cleared state and saved counters, then its seeds: one entry per
+// (target, fragment) of every publish (flood: every connection), scap at the most.
+static void lpull_begin(Ctx& c, const Batch& b, uint32_t K, const LpOpts& o, uint32_t N, uint64_t scap) {
+  const uint32_t N0 = c.cfg.peers;
+  const Slices* sl = o.sl;
   hipStream_t s = c.stream;
-  const size_t NL = (size_t)N * L;
-  const bool nolog = nl && nl->on;
-  if (nolog && (dense || idw || gos || chn || sl || b.FP != 1))
-    c.fail(GS_EINVAL, "internal: no-log list pass asked for a batch it cannot take");
-  c.d_lrec.alloc((chn ? 4 : 2) * NL);  // churn records are 16 B
+  const size_t NL = (size_t)N * b.L;
+  c.d_lrec.alloc((o.chn ? 4 : 2) * NL);  // churn records are 16 B
   c.d_lcnt.alloc(2 * (size_t)N);
   c.d_pctrl.alloc(LP_CT_WORDS);
-  const uint32_t ls = lpull_stride(b);
-  c.d_lblk.alloc((size_t)K * N * ls);
+  c.d_lblk.alloc((size_t)K * N * lpull_stride(b));
   c.d_lst.alloc((size_t)N * LP_SW);
   c.d_lfin.alloc((size_t)N * LP_FW);
-  if (!nolog) c.d_flane.alloc(NL);
+  if (!(o.nl && o.nl->on)) c.d_flane.alloc(NL);
   if (!c.rpos_valid) {
     c.d_rpos.alloc((size_t)N0 * MESH_W);
     GS_HIP(hipMemsetAsync(c.d_counters.p + C_ERR, 0, 8, s));
@@ -1170,8 +1216,6 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
   for (int q = 0; q < 3; q++) GS_HIP(hipMemsetAsync(c.d_pctrl.p + q * 4 + 3, 0xFF, 8, s));
   c.d_lp_save.alloc(C_COUNT);
   GS_HIP(hipMemcpyAsync(c.d_lp_save.p, c.d_counters.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
-  // seeds: one entry per (target, fragment) of every publish (flood: every connection)
-  const uint64_t scap = (uint64_t)(sl ? sl->S : 1) * b.B * b.Fe * std::max<uint64_t>(c.max_degree, MESH_W);
   c.d_skey.alloc(scap);
   c.d_slane.alloc(scap);
   c.d_scnt.alloc(1);
@@ -1181,9 +1225,16 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
       launch_seed(c, b, 0, N0, c.d_pctrl.p + 2 * 4 + 3, nullptr, true, sl->lpub + (size_t)j * b.B, j * N0);
   else
     launch_seed(c, b, 0, N, c.d_pctrl.p + 2 * 4 + 3, nullptr, true);
+}
+
+// The passes' arguments but for lazy gossip's (lpull_gos_args); churn: its per-row state, cleared.
+static LPullArgs lpull_args(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, const LpOpts& o, uint32_t N) {
+  const Slices* sl = o.sl;
+  const ChnRun* chn = o.chn;
+  hipStream_t s = c.stream;
   LPullArgs la{};
   la.keys = c.d_keys.p; la.flane = c.d_flane.p; la.busy = c.d_busy.p; la.blk = c.d_lblk.p;
-  if (nolog) la.keys = nullptr, la.flane = nullptr;  // (k_lpub's sign that no log is kept)
+  if (o.nl && o.nl->on) la.keys = nullptr, la.flane = nullptr;  // (k_lpub's sign that no log is kept)
   la.st = c.d_lst.p; la.fin = c.d_lfin.p;
   la.lrec = c.d_lrec.p; la.lcnt = c.d_lcnt.p; la.rpos = c.d_rpos.p;
   la.mesh = c.d_mesh.p; la.pub = c.d_pub.p; la.stage = c.d_stage.p; la.tables = c.d_tables.p;
@@ -1192,14 +1243,14 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
     la.rpos = c.d_srpos.p;
     la.stage = c.d_sstage.p;
     la.pub = sl->spub;
-    la.rN = N0;
+    la.rN = c.cfg.peers;
   }
   const uint64_t grain = pull_grain(b.tshift);
   la.ctrl = c.d_pctrl.p; la.counters = c.d_counters.p; la.delta = b.delta / grain * grain;
   la.tmax = b.tmax - grain;
-  la.N = N; la.B = b.B; la.L = L; la.S = c.S; la.sb = b.sb; la.tshift = b.tshift;
+  la.N = N; la.B = b.B; la.L = b.L; la.S = c.S; la.sb = b.sb; la.tshift = b.tshift;
   la.K = K; la.lb = lb; la.dG = (uint32_t)(la.delta / grain);
-  la.idw = idw ? 1u : 0u;
+  la.idw = o.idw ? 1u : 0u;
   la.rmax = lpull_rmax(b);
   la.ghk = ~0u;
   la.gsw = ~0u;  // (frozen mesh: every heartbeat's IHAVEs are decided by the receivers)
@@ -1235,95 +1286,57 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
     // (121 ms per batch without, 129 ms from heartbeat 4 on, 193 ms from 1 on)
     la.gsw = (uint32_t)env_int("GS_GOSSIP_SWITCH", ~0u);
   }
-  // test knobs, read per batch: GS_LPULL_CAP's small lists force the overflow re-run;
-  // GS_LPULL_CAP_BATCHES (comma-separated 0-based indices of the run's batch loop, in run
-  // order: after the class regrouping) keeps the cap to the listed batches
-  long cap = env_int("GS_LPULL_CAP", (long)ls);
-  const char* capb = getenv("GS_LPULL_CAP_BATCHES");
-  if (capb && *capb) {
-    bool listed = false;
-    for (const char* q = capb; *q && !listed;) {
-      char* end = nullptr;
-      const unsigned long long v = strtoull(q, &end, 10);
-      listed = end != q && v == c.run_batch;
-      q = end != q ? end : q + 1;
-      while (*q == ',' || *q == ' ') q++;
-    }
-    if (!listed) cap = (long)ls;
-  }
-  la.ls = ls;
-  la.lcap = (uint32_t)std::min<long>(std::max(1l, cap), (long)ls);
-  // 40 KB of LDS per block: 4 blocks (16 waves, 16 rows in flight) resident per
-  // CU. Large graphs launch up to 16 blocks per CU so that a pass's tail is
-  // made of short blocks, keeping >= 32 rows per wave (1M peers: 54.3 ms per
-  // step at 4 blocks per CU, 53.1 at 16; 100k peers: 7.8 ms at 16, 6.8 at 4;
-  // profiles/r02_v7/lpull_grid_sweep.txt)
-  // a power of two: 15 per CU measured 56.4 ms against 53.1 at 16 on one box
-  uint64_t auto_bpc = 4;
-  while (auto_bpc < 16 && (uint64_t)N >= (uint64_t)dev_cus * PULL_WAVES * 32 * auto_bpc * 2) auto_bpc *= 2;
-  const uint64_t want = (uint64_t)dev_cus * auto_bpc;  // whole blocks per CU
-  unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)N + PULL_WAVES - 1) / PULL_WAVES, want));
-  k_lseed<<<(unsigned)std::max<uint64_t>(1, std::min<uint64_t>((scap + TB - 1) / TB, (uint64_t)dev_cus * 4)), TB, 0, s>>>(
-      la, c.d_skey.p, c.d_slane.p, c.d_scnt.p);
-  {  // the rows whose emit step needs the publishers (LP_PUB)
-    la.pubw = 1;
-    const uint64_t nm = (uint64_t)(sl ? sl->S : 1u) * b.B, width = (chn ? CELL_W : MESH_W) + 1;
-    k_lpubnb<<<(unsigned)((nm * width + TB - 1) / TB), TB, 0, s>>>(la, (uint32_t)nm);
-  }
-  for (uint32_t j = 0; j < (sl ? sl->S : 1u); j++) {  // (a slice's publishers are its rows)
-    LPullArgs lj = la;
-    if (sl) lj.pub = sl->spub + (size_t)j * b.B;
-    k_lpub<<<(b.B * b.Fe + 255) / 256, 256, 0, s>>>(lj, b.Fe);
-  }
-  GS_HIP(hipGetLastError());
-  if (gos) {  // GOS: sender planes, row-done bits, heartbeat control (gs_lpull_kernel.h)
-    ensure_csrpos(c);
-    c.d_gpl.alloc((size_t)N * LP_FW);
-    c.d_gse.alloc(NL);
-    c.d_rowdone.alloc(((size_t)N + 31) / 32);
-    c.d_gctl.alloc(GC_WORDS);
-    GS_HIP(hipMemsetAsync(c.d_rowdone.p, 0, ((size_t)N + 31) / 32 * 4, s));
-    GS_HIP(hipMemsetAsync(c.d_gctl.p, 0, GC_WORDS * 8, s));
-    GS_HIP(hipMemcpyAsync(c.d_gctl.p + GC_FD0, c.d_counters.p + C_FD, 8, hipMemcpyDeviceToDevice, s));
-    GS_HIP(hipMemcpyAsync(c.d_gctl.p + GC_FDP, c.d_counters.p + C_FD, 8, hipMemcpyDeviceToDevice, s));
-    la.grel0 = gos->rel0;
-    la.ghb = gos->hb;
-    la.glat_min = b.lat_min;
-    la.glat_max = b.lat_max;
-    la.gnf = (uint64_t)(sl ? sl->S : 1u) * b.B * b.Fe * (N0 - 1);  // lanes that can be final, less the publishers'
-    la.F = b.F;
-    la.collide = b.collide ? 1u : 0u;
-    la.gseed = c.cfg.seed;
-    la.ghist = c.cfg.history_gossip;
-    la.gd_lazy = c.cfg.d_lazy;
-    la.ggf = c.cfg.gossip_factor_milli;
-    la.gctl = c.d_gctl.p;
-    la.gpl = c.d_gpl.p;
-    la.gse = c.d_gse.p;
-    la.rowdone = c.d_rowdone.p;
-    la.row = c.d_row.p;
-    la.col = c.d_col.p;
-    la.flags = c.d_flags.p;
-    la.csrpos = c.d_csrpos.p;
-    la.habs0 = c.d_habs0.p;
-  }
-  auto dispatch = [&] {
-    if (gos) lpull_dispatch_gos(la, grid, s);
-    else lpull_dispatch(b.FP, la, grid, s, nolog);
-  };
+  la.ls = lpull_stride(b);
+  la.lcap = lpull_cap(c, la.ls);
+  return la;
+}
+
+// GOS: sender planes, row-done bits, heartbeat control (gs_lpull_kernel.h)
+static void lpull_gos_args(Ctx& c, const Batch& b, const LpOpts& o, LPullArgs& la) {
+  const uint32_t N = la.N;
+  hipStream_t s = c.stream;
+  ensure_csrpos(c);
+  c.d_gpl.alloc((size_t)N * LP_FW);
+  c.d_gse.alloc((size_t)N * b.L);
+  c.d_rowdone.alloc(((size_t)N + 31) / 32);
+  c.d_gctl.alloc(GC_WORDS);
+  GS_HIP(hipMemsetAsync(c.d_rowdone.p, 0, ((size_t)N + 31) / 32 * 4, s));
+  GS_HIP(hipMemsetAsync(c.d_gctl.p, 0, GC_WORDS * 8, s));
+  GS_HIP(hipMemcpyAsync(c.d_gctl.p + GC_FD0, c.d_counters.p + C_FD, 8, hipMemcpyDeviceToDevice, s));
+  GS_HIP(hipMemcpyAsync(c.d_gctl.p + GC_FDP, c.d_counters.p + C_FD, 8, hipMemcpyDeviceToDevice, s));
+  la.grel0 = o.gos->rel0;
+  la.ghb = o.gos->hb;
+  la.glat_min = b.lat_min;
+  la.glat_max = b.lat_max;
+  // lanes that can be final, less the publishers'
+  la.gnf = (uint64_t)(o.sl ? o.sl->S : 1u) * b.B * b.Fe * (c.cfg.peers - 1);
+  la.F = b.F;
+  la.collide = b.collide ? 1u : 0u;
+  la.gseed = c.cfg.seed;
+  la.ghist = c.cfg.history_gossip;
+  la.gd_lazy = c.cfg.d_lazy;
+  la.ggf = c.cfg.gossip_factor_milli;
+  la.gctl = c.d_gctl.p;
+  la.gpl = c.d_gpl.p;
+  la.gse = c.d_gse.p;
+  la.rowdone = c.d_rowdone.p;
+  la.row = c.d_row.p;
+  la.col = c.d_col.p;
+  la.flags = c.d_flags.p;
+  la.csrpos = c.d_csrpos.p;
+  la.habs0 = c.d_habs0.p;
+}
+
+// Passes in groups of 8 until one decides DONE (one host read of the control slots, the
+// error word and, no-log, the batch words per group) or a list is lost. Returns the
+// passes run; c.h_pinned holds the last read.
+static uint32_t lpull_passes(Ctx& c, uint32_t FP, LPullArgs& la, unsigned grid, bool gos, bool nolog) {
+  hipStream_t s = c.stream;
   uint32_t pass = 0;
   for (;;) {
     for (uint32_t q = 0; q < 8; q++) {
       la.pass = pass++;
-      if (c.timing) {  // (start, mid, end): the whole pass is frontier time
-        GS_HIP(hipEventRecord(ev(n_ev), s));
-        GS_HIP(hipEventRecord(ev(n_ev + 1), s));
-        dispatch();
-        GS_HIP(hipEventRecord(ev(n_ev + 2), s));
-        n_ev += 3;
-      } else {
-        dispatch();
-      }
+      timed_pass(c, s, [&] { lpull_dispatch(FP, la, grid, s, gos, nolog); });
     }
     GS_HIP(hipGetLastError());
     GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_pctrl.p, 12 * 8, hipMemcpyDeviceToHost, s));
@@ -1344,7 +1357,43 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
     if (c.h_pinned[((pass - 1) % 3) * 4 + 1] == PM_DONE) break;
     if (c.h_pinned[12] & (ERR_LIST | ERR_RING)) break;  // lost already: stop early, re-run on k_pull
   }
-  c.stats.relax_launches += pass;
+  return pass;
+}
+
+// One batch on the list pull path: k_seed appends the first sends to a seed
+// list (no dense key table to reset), k_lseed files them into the candidate
+// lists, k_lpub logs the publishers' own lanes, then passes in chunks of 8 as
+// on the k_pull path; completion reads the final logs (k_lcomplete) unless a
+// caller needs dense rows (k_lfinal).
+// Returns false (counters restored) when a list overflowed: the caller re-runs
+// the batch on k_pull.
+static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, const LpOpts& o) {
+  const Slices* sl = o.sl;
+  NoLog* nl = o.nl;
+  const uint32_t N = sl ? sl->S * c.cfg.peers : c.cfg.peers;  // the pass's rows
+  hipStream_t s = c.stream;
+  const bool nolog = nl && nl->on;
+  if (nolog && (o.dense || o.idw || o.gos || o.chn || sl || b.FP != 1))
+    c.fail(GS_EINVAL, "internal: no-log list pass asked for a batch it cannot take");
+  const uint64_t scap = (uint64_t)(sl ? sl->S : 1) * b.B * b.Fe * std::max<uint64_t>(c.max_degree, MESH_W);
+  lpull_begin(c, b, K, o, N, scap);
+  LPullArgs la = lpull_args(c, b, K, lb, o, N);
+  const unsigned grid = lpull_grid(N, c.num_cus);
+  k_lseed<<<(unsigned)std::max<uint64_t>(1, std::min<uint64_t>((scap + TB - 1) / TB, (uint64_t)c.num_cus * 4)), TB, 0, s>>>(
+      la, c.d_skey.p, c.d_slane.p, c.d_scnt.p);
+  {  // the rows whose emit step needs the publishers (LP_PUB)
+    la.pubw = 1;
+    const uint64_t nm = (uint64_t)(sl ? sl->S : 1u) * b.B, width = (o.chn ? CELL_W : MESH_W) + 1;
+    k_lpubnb<<<(unsigned)((nm * width + TB - 1) / TB), TB, 0, s>>>(la, (uint32_t)nm);
+  }
+  for (uint32_t j = 0; j < (sl ? sl->S : 1u); j++) {  // (a slice's publishers are its rows)
+    LPullArgs lj = la;
+    if (sl) lj.pub = sl->spub + (size_t)j * b.B;
+    k_lpub<<<(b.B * b.Fe + 255) / 256, 256, 0, s>>>(lj, b.Fe);
+  }
+  GS_HIP(hipGetLastError());
+  if (o.gos) lpull_gos_args(c, b, o, la);
+  c.stats.relax_launches += lpull_passes(c, b.FP, la, grid, o.gos != nullptr, nolog);
   if (c.h_pinned[12] & (ERR_LIST | ERR_RING)) {  // the error word as of the last pass read
     GS_HIP(hipMemcpyAsync(c.d_counters.p, c.d_lp_save.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
     return false;
@@ -1362,15 +1411,15 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, EvF
   c.stats.list_pull_batches++;
   if (dbg_comp)
     fprintf(stderr, "[lp] batch %llu: completion %s\n", (unsigned long long)c.run_batch,
-            nolog ? "in-pass (no log)" : idw ? "dense keys (idontwant)" : dense ? "dense rows (k_lfinal)" : "final log");
+            nolog ? "in-pass (no log)" : o.idw ? "dense keys (idontwant)" : o.dense ? "dense rows (k_lfinal)" : "final log");
   if (nolog) {  // nothing to complete: no log was written, the counters are added
     nl->tmax = c.h_pinned[13];
     nl->deliv = c.h_pinned[14];
     c.keys_none = true;
     return true;
   }
-  if (idw) return true;  // the final keys are dense rows already
-  if (dense) {  // a sink, the traffic pass or a fragment group needs [N][L] rows
+  if (o.idw) return true;  // the final keys are dense rows already
+  if (o.dense) {  // a sink, the traffic pass or a fragment group needs [N][L] rows
     k_lfinal<<<grid, TB, 0, s>>>(la);
     GS_HIP(hipGetLastError());
   } else {
@@ -1575,8 +1624,7 @@ static void ensure_ring(Ctx& c) {
   if (gossip) c.d_ring_in.alloc((size_t)c.ring_R * N * GT_IN);  // inverse IHAVE lists (ring_in_lists)
 }
 
-static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, const gs_result_sink* sink,
-                              const std::vector<uint8_t>* cut);
+#include "gs_run.h"
 
 // Schedules that are not lockstep: the churn list pass and the
 // gossip inside the list pass need every message of a batch at the same
@@ -1598,29 +1646,18 @@ static bool class_plan(Ctx& c, const gs_publish* sched, uint64_t n, const gs_res
   if (sink && (sink->on_block || sink->on_lat)) return false;
   if (env_off("GS_CLASS_SPLIT")) return false;
   constexpr uint64_t cmax = 64;
-  const uint64_t hb = c.cfg.heartbeat_ns, ph = c.cfg.hb_phase_ns;
   for (uint64_t i = 0; i < n; i++)
-    if (sched[i].t_pub_ns < ph) return false;  // (run_messages_impl reports what it must)
+    if (sched[i].t_pub_ns < c.cfg.hb_phase_ns) return false;  // (Run reports what it must)
   if (churn) ensure_ring(c);
-  const uint32_t Bmax = c.cfg.batch;
   perm.resize(n);
   cut.assign(n, 0);
   bool any = false;
   for (uint64_t g0 = 0; g0 < n;) {  // a group: what one batch could hold
     const uint32_t F0 = frags_of(c, sched[g0]);
-    const uint64_t cap = std::max<uint32_t>(1, std::min<uint32_t>(Bmax, PULL_LMAX / pow2_at_least(F0)));
-    uint64_t g1 = g0 + 1, lo = (sched[g0].t_pub_ns - ph) / hb, hi = lo;
-    while (g1 < n && g1 - g0 < cap && sched[g1].msg_size == sched[g0].msg_size && frags_of(c, sched[g1]) == F0) {
-      if (churn) {
-        const uint64_t ep = (sched[g1].t_pub_ns - ph) / hb, lo2 = std::min(lo, ep), hi2 = std::max(hi, ep);
-        if (hi2 + c.cfg.churn_horizon - lo2 + 1 > c.ring_R) break;
-        lo = lo2;
-        hi = hi2;
-      }
-      g1++;
-    }
+    uint64_t lo = 0, hi = 0;
+    const uint64_t g1 = same_shape_end(c, sched, n, g0, pull_batch_cap(c.cfg.batch, F0), nullptr, churn, lo, hi);
     std::vector<std::pair<uint64_t, uint64_t>> key(g1 - g0);  // (offset class, message)
-    for (uint64_t i = g0; i < g1; i++) key[i - g0] = {(sched[i].t_pub_ns - ph) % hb, i};
+    for (uint64_t i = g0; i < g1; i++) key[i - g0] = {hb_pos(c, sched[i].t_pub_ns).off, i};
     std::stable_sort(key.begin(), key.end(), [](const std::pair<uint64_t, uint64_t>& x,
                                                  const std::pair<uint64_t, uint64_t>& y) { return x.first < y.first; });
     uint64_t ncls = 1;
@@ -1640,10 +1677,10 @@ static bool class_plan(Ctx& c, const gs_publish* sched, uint64_t n, const gs_res
 void run_messages(Ctx& c, const gs_publish* sched, uint64_t n_msgs, const gs_result_sink* sink) {
   std::vector<uint64_t> perm;
   std::vector<uint8_t> cut;
-  if (!class_plan(c, sched, n_msgs, sink, perm, cut)) return run_messages_impl(c, sched, n_msgs, sink, nullptr);
+  if (!class_plan(c, sched, n_msgs, sink, perm, cut)) return Run(c, sched, n_msgs, sink, nullptr).run();
   std::vector<gs_publish> ps(n_msgs);
   for (uint64_t i = 0; i < n_msgs; i++) ps[i] = sched[perm[i]];
-  if (!sink) return run_messages_impl(c, ps.data(), n_msgs, nullptr, &cut);
+  if (!sink) return Run(c, ps.data(), n_msgs, nullptr, &cut).run();
   // the results in class order, then every row back to its message
   const uint32_t N = c.cfg.peers;
   gs_result_sink ts = *sink;
@@ -1653,7 +1690,7 @@ void run_messages(Ctx& c, const gs_publish* sched, uint64_t n_msgs, const gs_res
   ts.t_complete_ns = sink->t_complete_ns ? tc.data() : nullptr;
   ts.hops = sink->hops ? hp.data() : nullptr;
   ts.summary = sink->summary ? sm.data() : nullptr;
-  run_messages_impl(c, ps.data(), n_msgs, &ts, &cut);
+  Run(c, ps.data(), n_msgs, &ts, &cut).run();
   for (uint64_t i = 0; i < n_msgs; i++) {
     const uint64_t m = perm[i];
     if (sink->t_complete_ns) memcpy(sink->t_complete_ns + m * N, tc.data() + i * N, (size_t)N * 8);
@@ -1662,939 +1699,6 @@ void run_messages(Ctx& c, const gs_publish* sched, uint64_t n_msgs, const gs_res
   }
 }
 
-static void run_messages_impl(Ctx& c, const gs_publish* sched, uint64_t n_msgs, const gs_result_sink* sink,
-                              const std::vector<uint8_t>* cut) {
-  const uint32_t N = c.cfg.peers;
-  const uint32_t Bmax = c.cfg.batch;
-  hipStream_t s = c.stream;
-  if (c.lat_pend.on) {  // left by a run that failed: its lines are not handed out
-    GS_HIP(hipStreamSynchronize(c.copy));
-    c.lat_pend.on = false;
-  }
-  c.lat_async = true;
-  struct AsyncOff {
-    Ctx& c;
-    int unwinding0 = std::uncaught_exceptions();
-    ~AsyncOff() {
-      c.lat_async = false;
-      //  a run that fails after a batch completed still hands out that
-      // batch's pending latency lines, as the synchronous sink did before; nothing
-      // here may throw while the error unwinds
-      Ctx::LatPending& p = c.lat_pend;
-      if (std::uncaught_exceptions() <= unwinding0 || !p.on) return;
-      p.on = false;
-      if (hipEventSynchronize(c.lat_done[p.par]) != hipSuccess || (c.h_laterr[p.par] & ERR_LAT16)) return;
-      for (uint32_t q0 = 0; q0 < p.B; q0 += p.bm) {
-        const uint32_t n = std::min(p.bm, p.B - q0);
-        p.sink->on_lat(p.sink->user, p.row0 + q0, n, p.un, c.h_lat[p.par] + (size_t)q0 * p.un);
-      }
-    }
-  } async_off{c};
-  // Churn runs (config #3): the epoch chain is latency-bound and runs as fast on
-  // one XCD's 32 CUs as on all 256 (one L2 holds its per-peer state; bits 0..31
-  // of the CU mask, 4 CUs on each XCD, take twice as long), and the list pass at
-  // 100k peers as fast on 7 XCDs (or 4) as on 8 (profiles/r06_chain). So the
-  // chain gets its own XCD (c.chain_pipe, GS_CHAIN_XCDS, default XCD 0) and the
-  // rest of the run the others (c.pass_ms, GS_PASS_XCDS, default 1-7): the next
-  // batch's chain then runs beside this batch's passes (ChnAhead below).
-  // GS_CHN_PIPE=0 keeps one stream (GS_PASS_XCDS alone then still moves the passes).
-  ensure_cus(c);
-  const bool pipe_on = c.cfg.churn_ppm && !env_off("GS_CHN_PIPE") && c.num_cus == 256 &&
-                       c.cfg.flood_publish && !c.traffic && !c.sink_dev && !getenv("GS_DEBUG_CHN");
-  struct PassStream {
-    Ctx& c;
-    hipStream_t orig = nullptr;
-    PassStream(Ctx& cc, bool pipe) : c(cc) {
-      uint32_t px = xcd_env("GS_PASS_XCDS");
-      if (pipe) {
-        if (!c.chain_pipe) {
-          const uint32_t cx = xcd_env("GS_CHAIN_XCDS");
-          c.chain_pipe = xcd_stream(c, cx ? cx : 0x01u);
-        }
-        if (!px) px = 0xFEu & ~xcd_env("GS_CHAIN_XCDS");
-      }
-      if (!px) return;
-      if (!c.pass_ms) {  // created once per context (a CU-masked stream costs ~10 ms)
-        c.pass_ms = xcd_stream(c, px);
-        for (auto& ev : c.pass_ev) GS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      }
-      orig = c.stream;
-      GS_HIP(hipEventRecord(c.pass_ev[0], orig));
-      GS_HIP(hipStreamWaitEvent(c.pass_ms, c.pass_ev[0], 0));
-      c.stream = c.pass_ms;
-    }
-    ~PassStream() {
-      if (!orig) return;
-      (void)hipEventRecord(c.pass_ev[1], c.pass_ms);
-      (void)hipStreamWaitEvent(orig, c.pass_ev[1], 0);
-      (void)hipStreamSynchronize(orig);
-      c.stream = orig;
-    }
-  } pass_stream{c, pipe_on};
-  s = c.stream;
-  GS_HIP(hipMemsetAsync(c.d_counters.p + C_ERR, 0, 8, s));
-  check_schedule(c, sched, n_msgs);
-  uint32_t Fmax = 1;
-  for (uint64_t i = 0; i < n_msgs; i++) Fmax = std::max(Fmax, frags_of(c, sched[i]));
-  const uint32_t FPmax = pow2_at_least(Fmax);
-  const long var_env = env_int("GS_RELAX_VARIANT", -1);  // a bit mask; unset (< 0): the default below
-  // default: owner-computes pull over candidate lists (64 | 32), fragmented batches
-  // too (128; config #2 7.2e8 against 6.7e8/s on k_pull's dense rows, round 4);
-  // k_pull's dense rows without 64; without 32 the push path: split (8) + final
-  // bitset (4) + read filter (1)
-  uint32_t variant = var_env < 0 ? 237u : (uint32_t)var_env;
-  const bool lanes32 = (uint64_t)N * Bmax * FPmax < (1ull << 32);  // frontier indices are u32
-  if (!lanes32) variant &= ~8u;
-  const bool gossip = c.cfg.lazy_gossip != 0;
-  // the pull path needs rows in LDS and one mesh per batch (churn uses one per
-  // epoch: the push path). IDONTWANT batches run on the list pass with dense
-  // final keys (k_lpull<FP, CH, true>; rows of fragment groups with bit 128),
-  // else on the push path. Lazy gossip runs on the pull path when the batch
-  // proves it a no-op (gossip_noop), else the batch is re-run on the push path.
-  const bool churn = c.cfg.churn_ppm != 0;  // per-epoch mesh lookups live on the push path
-  const bool pull_any = (variant & 32) && !churn;
-  // churn on the list pass (gs_cpull.h): lockstep batches (rows of fragment groups
-  // included) without IDONTWANT, CSR rows of <= 64 entries (<= 58 with lazy gossip: the IHAVE entry's
-  // target mask); GS_CHURN_LIST=0 keeps them on the push path
-  const bool chn_any = churn && (variant & 32) && (variant & 64) && !env_off("GS_CHURN_LIST") &&
-                       c.max_degree <= (gossip ? GSE_HOPS : CELL_W) && N < (1u << 21);
-  // the push path with gossip or churn runs split, without tile skip
-  // the push path with gossip or churn runs split + tile skip (its long tail of
-  // IHAVE and churn buckets touches few tiles); GS_RELAX_VARIANT can turn the skip off
-  const uint32_t pvariant = (gossip || churn) ? (((variant | 8u) & ~32u) | (var_env < 0 ? 2u : 0u))
-                                              : (variant & ~32u);
-  if (churn && !lanes32) c.fail(GS_EUNSUPPORTED, "churn needs peers*batch*FP < 2^32");
-  std::vector<uint64_t> q0v(Bmax), r0v(Bmax), ep(churn ? n_msgs : 0);
-  if (churn) {  // epoch of every publish; the snapshot ring
-    const uint64_t hb = c.cfg.heartbeat_ns, ph = c.cfg.hb_phase_ns;
-    for (uint64_t i = 0; i < n_msgs; i++) {
-      if (sched[i].t_pub_ns < ph || (sched[i].t_pub_ns - ph) / hb >= (1ull << 20))
-        c.fail(GS_EINVAL, "churn needs every publish within 2^20 heartbeats after hb_phase_ns");
-      ep[i] = (sched[i].t_pub_ns - ph) / hb;
-    }
-    ensure_ring(c);
-  }
-  const size_t max_tiles = ((size_t)N * Bmax * FPmax + 63) / 64;
-  c.d_keys.alloc((size_t)N * Bmax * FPmax);
-  c.d_meta.alloc(max_tiles * sizeof(TileMeta) / 8);
-  c.d_fbits.alloc(max_tiles);
-  if (FPmax > 1) c.d_busy.alloc((size_t)N * Bmax);
-  c.d_tc.alloc((size_t)N * Bmax);
-  c.d_hops.alloc((size_t)N * Bmax);
-  c.d_cnt_save.alloc(C_COUNT);
-  std::vector<uint64_t> rel0(Bmax), habs0(Bmax);
-  std::vector<uint8_t> malive(Bmax);
-  uint64_t g0 = INF64;
-  // Timing events come from a per-context pool: [0] run start, [1] run end,
-  // then one (start, scan end, end) triple around every relaxation launch.
-  size_t n_ev = 0;
-  auto ev = [&](size_t i) {
-    while (c.ev_pool.size() <= i) {
-      hipEvent_t e;
-      GS_HIP(hipEventCreate(&e));
-      c.ev_pool.push_back(e);
-    }
-    return c.ev_pool[i];
-  };
-  if (c.timing) {
-    GS_HIP(hipEventRecord(ev(0), s));
-    ev(1);
-    n_ev = 2;
-  }
-  ensure_cus(c);
-  const int dev_cus = c.num_cus;
-  // Batch slices: consecutive full batches of one shape on a small graph run as
-  // one list pass over S copies of the graph (run_lpull_batch's Slices), so that
-  // a launch has S x N rows instead of N: a pass of a few rows per resident wave
-  // is mostly latency (config #2's 10k-peer F = 8 rows: 98 us per pass at 10k
-  // rows, 340 us at 80k; scripts/c2_probe.py). Frozen mesh, no IDONTWANT, no
-  // per-peer traffic; lazy gossip through the eager pass's no-op proof, per slice,
-  // and when that fails (or failed before: glp_prefer) inside the group's passes
-  // as run_glp does, if the whole group is lockstep (else single batches take
-  // it). GS_SLICES=0 turns them off, GS_SLICES=n caps a group at n slices.
-  const uint32_t sl_max = (uint32_t)std::max(0l, env_int("GS_SLICES", 64));
-  constexpr uint64_t SL_ROWS = 1ull << 19;  // rows per pass a group aims at (memory: ~S x N x L x 40 B)
-  uint64_t slice_skip = 0;                  // messages before it run as single batches
-  auto try_slices = [&](uint64_t i0, uint64_t& i_end) -> bool {
-    if (sl_max < 2 || !pull_any || !(variant & 64) || c.traffic || (uint64_t)N * 2 >= (1u << 21)) return false;
-    const uint32_t F0 = frags_of(c, sched[i0]), FP0 = pow2_at_least(F0);
-    if (FP0 > 1 && !(variant & 128)) return false;
-    const uint32_t Bc = std::min<uint32_t>(Bmax, PULL_LMAX / FP0);
-    const uint64_t s_cap = std::min<uint64_t>({(uint64_t)sl_max, std::max<uint64_t>(1, SL_ROWS / N), ((1ull << 21) - 1) / N});
-    uint64_t n_same = 1;  // messages of this shape from i0 (as far as a group can take)
-    while (n_same < s_cap * Bc && i0 + n_same < n_msgs && !(cut && (*cut)[i0 + n_same]) &&
-           sched[i0 + n_same].msg_size == sched[i0].msg_size &&
-           frags_of(c, sched[i0 + n_same]) == F0)
-      n_same++;
-    const uint32_t S = (uint32_t)std::min<uint64_t>(n_same / Bc, s_cap);
-    if (S < 2) return false;
-    slice_skip = i0 + (uint64_t)S * Bc;  // unless the group completes below
-    std::vector<Batch> bs(S);
-    std::vector<uint32_t> spub((size_t)S * Bc), lpub((size_t)S * Bc);
-    for (uint32_t j = 0; j < S; j++) {
-      const uint64_t q0 = i0 + (uint64_t)j * Bc;
-      bs[j] = setup_batch(c, sched, q0, q0 + Bc, j == 0);
-      for (uint32_t q = 0; q < Bc; q++) {
-        lpub[(size_t)j * Bc + q] = sched[q0 + q].publisher;
-        spub[(size_t)j * Bc + q] = sched[q0 + q].publisher + j * N;
-      }
-    }
-    Batch g = bs[0];  // the slices' keys: the source field holds slice rows (S x N ids)
-    g.sb = bits_for(S * N);
-    g.tshift = g.sb + HOP_BITS;
-    g.tmax = g.tshift >= 64 ? 0 : (INF64 >> g.tshift);
-    for (Batch& bj : bs) {
-      bj.sb = g.sb;
-      bj.tshift = g.tshift;
-      bj.tmax = g.tmax;
-    }
-    if (c.cfg.idontwant && g.payload >= c.cfg.idontwant) return false;
-    const uint64_t grain = pull_grain(g.tshift);
-    if (g.delta < grain) return false;
-    std::vector<uint64_t> stp((size_t)S * Bc);
-    for (uint32_t j = 0; j < S; j++) std::copy(bs[j].tpub.begin(), bs[j].tpub.end(), stp.begin() + (size_t)j * Bc);
-    // lazy gossip inside the passes (the group's IHAVE / IWANT as run_glp's): every
-    // message of the group has its heartbeats at the same time after its publish
-    std::vector<uint64_t> rel(stp.size()), hab(stp.size());
-    bool lock = gossip;
-    if (gossip) {
-      const uint64_t hb = c.cfg.heartbeat_ns, ph = c.cfg.hb_phase_ns;
-      for (size_t q = 0; q < stp.size(); q++) {
-        const uint64_t tp = stp[q], h0 = tp <= ph ? 0 : (tp - ph + hb - 1) / hb;
-        rel[q] = ph + h0 * hb - tp;
-        hab[q] = h0;
-        lock = lock && rel[q] == rel[0];
-      }
-    }
-    Batch gg = g;
-    gg.delta = std::min(g.delta, g.lat_min);
-    const bool glp_ok = lock && !env_off("GS_GOSSIP_LIST") && c.max_degree <= GSE_HOPS &&
-                        gg.delta >= grain && c.cfg.heartbeat_ns > g.lat_max + gg.delta;
-    if (gossip && c.glp_prefer && !glp_ok) return false;  // single batches (the push path)
-    const size_t NR = (size_t)S * N;
-    c.d_spub.alloc(spub.size());
-    c.d_lpub.alloc(lpub.size());
-    c.d_stpub.alloc(stp.size());
-    GS_HIP(hipMemcpyAsync(c.d_spub.p, spub.data(), spub.size() * 4, hipMemcpyHostToDevice, s));
-    GS_HIP(hipMemcpyAsync(c.d_lpub.p, lpub.data(), lpub.size() * 4, hipMemcpyHostToDevice, s));
-    GS_HIP(hipMemcpyAsync(c.d_stpub.p, stp.data(), stp.size() * 8, hipMemcpyHostToDevice, s));
-    c.d_keys.alloc(NR * g.L);
-    if (g.FP > 1) c.d_busy.alloc(NR * Bc);
-    auto fresh = [&] {  // per-run state of the group's pass
-      c.keys_log = c.keys_none = false;
-      if (g.FP > 1) GS_HIP(hipMemsetAsync(c.d_busy.p, 0, NR * Bc * 8, s));
-    };
-    const SinkWants sw = sink_wants(sink);
-    const bool dense = sw.rows() || sw.summary || getenv("GS_LPULL_DENSE");
-    const bool wants = sw.rows() || sw.lat || sw.summary;
-    const Slices sl{S, N, c.d_spub.p, c.d_lpub.p};
-    auto slice_in = [&](uint32_t j) {  // slice j's publishers and publish times where completion reads them
-      GS_HIP(hipMemcpyAsync(c.d_pub.p, lpub.data() + (size_t)j * Bc, Bc * 4, hipMemcpyHostToDevice, s));
-      GS_HIP(hipMemcpyAsync(c.d_tpub.p, bs[j].tpub.data(), Bc * 8, hipMemcpyHostToDevice, s));
-    };
-    auto finish = [&] {  // completion of a group whose keys stand
-      if (!wants) {  // device-resident results: the counters only
-        if (c.keys_log) run_complete(c, bs[0], 0, N, false, false, false, false, 0, c.d_lpub.p, c.d_stpub.p, S);
-        else
-          for (uint32_t j = 0; j < S; j++)
-            run_complete(c, bs[j], 0, N, false, false, false, false, (size_t)j * N, c.d_lpub.p + (size_t)j * Bc,
-                         c.d_stpub.p + (size_t)j * Bc);
-      } else {
-        for (uint32_t j = 0; j < S; j++) {
-          slice_in(j);
-          launch_complete(c, bs[j], 0, N, sink, i0 + (uint64_t)j * Bc, (size_t)j * N);
-        }
-      }
-    };
-    auto run_glp_group = [&]() -> bool {  // the gossip inside the group's passes
-      uint32_t lbg = 0;
-      const uint32_t Kg = lpull_ring(c, gg, gg.delta / grain * grain, &lbg, true, false, S * N);
-      if (!Kg) return false;
-      fresh();
-      c.d_habs0.alloc(std::max<size_t>(Bmax, hab.size()));
-      GS_HIP(hipMemcpyAsync(c.d_habs0.p, hab.data(), hab.size() * 8, hipMemcpyHostToDevice, s));
-      const GosRun gr{rel[0], c.cfg.heartbeat_ns};
-      const uint64_t iw0 = read_counter(c, C_GOSSIP);
-      if (!run_lpull_batch(c, gg, Kg, lbg, ev, n_ev, dev_cus, dense, false, &gr, nullptr, &sl)) return false;
-      c.stats.list_pull_batches += S - 1;
-      c.stats.gossip_list_batches += S;
-      if (read_counter(c, C_GOSSIP) != iw0) c.glp_quiet = 0;  // (run_glp's rule, per batch of the group)
-      else if ((c.glp_quiet += S) >= GLP_QUIET) c.glp_prefer = false;
-      finish();
-      return true;
-    };
-    bool ok = false;
-    if (gossip && c.glp_prefer) {
-      ok = run_glp_group();
-    } else {
-      uint32_t lb = 0;
-      const uint32_t K = lpull_ring(c, g, g.delta / grain * grain, &lb, false, false, S * N);
-      if (!K) return false;
-      fresh();
-      if (gossip) GS_HIP(hipMemcpyAsync(c.d_cnt_save.p, c.d_counters.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
-      if (!run_lpull_batch(c, g, K, lb, ev, n_ev, dev_cus, dense, false, nullptr, nullptr, &sl))
-        return false;  // (a list overflowed: counters restored; single batches take the messages)
-      c.stats.list_pull_batches += S - 1;
-      if (!gossip) {
-        finish();
-        ok = true;
-      } else {  // the eager result stands only if gossip is a no-op in every slice
-        // every slice's reductions into one pinned buffer, one wait
-        const size_t msb = (size_t)S * Bc * MS_COLS * 8;
-        if (c.h_slms_bytes < msb) {
-          if (c.h_slms) GS_HIP(hipHostFree(c.h_slms));
-          c.h_slms = nullptr;
-          c.h_slms_bytes = 0;
-          GS_HIP(hipHostMalloc((void**)&c.h_slms, msb, hipHostMallocDefault));
-          c.h_slms_bytes = msb;
-        }
-        if (c.keys_log) {  // every slice in one launch
-          run_complete(c, bs[0], 0, N, true, false, false, false, 0, c.d_lpub.p, c.d_stpub.p, S);
-          GS_HIP(hipMemcpyAsync(c.h_slms, c.d_mstat.p, msb, hipMemcpyDeviceToHost, s));
-        } else {
-          for (uint32_t j = 0; j < S; j++) {
-            run_complete(c, bs[j], 0, N, true, false, false, false, (size_t)j * N, c.d_lpub.p + (size_t)j * Bc,
-                         c.d_stpub.p + (size_t)j * Bc);
-            GS_HIP(hipMemcpyAsync(c.h_slms + (size_t)j * Bc * MS_COLS, c.d_mstat.p, (size_t)Bc * MS_COLS * 8,
-                                  hipMemcpyDeviceToHost, s));
-          }
-        }
-        GS_HIP(hipStreamSynchronize(s));
-        bool noop = true;
-        for (uint32_t j = 0; j < S && noop; j++) {
-          const std::vector<uint64_t> r0(rel.begin() + (size_t)j * Bc, rel.begin() + (size_t)(j + 1) * Bc);
-          noop = gossip_noop(bs[j], c.h_slms + (size_t)j * Bc * MS_COLS, r0);
-        }
-        if (noop) {
-          c.stats.gossip_noop_msgs += (uint64_t)S * Bc;
-          if (wants) {  // the sink's results: completion again per slice, its counters not counted twice
-            c.d_cnt_save2.alloc(C_COUNT);
-            GS_HIP(hipMemcpyAsync(c.d_cnt_save2.p, c.d_counters.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
-            for (uint32_t j = 0; j < S; j++) {
-              slice_in(j);
-              launch_complete(c, bs[j], 0, N, sink, i0 + (uint64_t)j * Bc, (size_t)j * N);
-            }
-            GS_HIP(hipMemcpyAsync(c.d_counters.p, c.d_cnt_save2.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
-          }
-          ok = true;
-        } else {  // gossip changes the group: discard the eager run; the gossip inside the passes takes it
-          GS_HIP(hipMemcpyAsync(c.d_counters.p, c.d_cnt_save.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
-          c.stats.list_pull_batches -= S;
-          if (glp_ok) {  // (without the in-pass gossip the single batches take it: they count their own)
-            c.stats.gossip_fallback_batches++;
-            c.glp_prefer = true;
-            c.glp_quiet = 0;
-            ok = run_glp_group();
-          }
-        }
-      }
-    }
-    if (!ok) return false;
-    GS_HIP(hipStreamSynchronize(s));  // (lpub / tpub / habs0 host copies die here)
-    c.stats.messages += (uint64_t)S * Bc;
-    c.stats.batches += S;
-    i_end = i0 + (uint64_t)S * Bc;
-    return true;
-  };
-  // a batch: up to B messages of equal size and chunk count (serialisation
-  // tables and the lane layout are per batch); the pull path holds a row in
-  // registers, so its batch is capped at PULL_LMAX / FP messages. Returns the
-  // end; churn: the batch's publish epochs [h_lo, h_hi] (+ lifetime) fit the ring.
-  auto form = [&](uint64_t a0, uint64_t& h_lo, uint64_t& h_hi) -> uint64_t {
-    const uint32_t F0 = frags_of(c, sched[a0]);
-    const uint32_t Bcap = pull_any || (chn_any && F0 == 1)
-                              ? std::max<uint32_t>(1, std::min<uint32_t>(Bmax, PULL_LMAX / pow2_at_least(F0)))
-                              : Bmax;
-    uint64_t a1 = a0 + 1;
-    h_lo = churn ? ep[a0] : 0;
-    h_hi = churn ? ep[a0] : 0;
-    while (a1 < n_msgs && a1 - a0 < Bcap && !(cut && (*cut)[a1]) && sched[a1].msg_size == sched[a0].msg_size &&
-           frags_of(c, sched[a1]) == F0) {
-      if (churn) {
-        const uint64_t lo2 = std::min(h_lo, ep[a1]), hi2 = std::max(h_hi, ep[a1]);
-        if (hi2 + c.cfg.churn_horizon - lo2 + 1 > c.ring_R) break;
-        h_lo = lo2;
-        h_hi = hi2;
-      }
-      a1++;
-    }
-    return a1;
-  };
-  // churn: the batch runs on the churn list pass (gs_cpull.h) — lockstep
-  // batches (fragment groups included) without IDONTWANT whose windows fit the rules
-  auto chn_decide = [&](const Batch& bb, const uint64_t* r0, uint64_t h_lo, uint64_t h_hi) -> bool {
-    if (!chn_any || bb.collide || !c.d_ring_mm.p) return false;
-    const uint64_t hb = c.cfg.heartbeat_ns;
-    const bool idw = c.cfg.idontwant && bb.payload >= c.cfg.idontwant;
-    bool lock = true;
-    for (uint32_t q = 1; q < bb.B && lock; q++) lock = r0[q] == r0[0];
-    const uint64_t dl = gossip ? std::min(bb.delta, bb.lat_min) : bb.delta;
-    const uint64_t cE = h_hi + c.cfg.churn_horizon - h_lo + 1;
-    return !idw && lock && cE <= 4096 && dl >= pull_grain(bb.tshift) && hb > lpull_rmax(bb) + 2 * dl &&
-           (!gossip || hb > bb.lat_max + dl);
-  };
-  // ChnAhead: the next churn list-pass batch's epoch chain and tables, enqueued
-  // on the chain's XCD (c.chain_pipe) while this batch's passes run on the
-  // others (the host enqueues the chain in slices between pass groups, at most
-  // AH_LEAD epochs ahead of what the GPU finished). The list pass reads only the
-  // batch tables, so the chain may overwrite ring slots of the batch whose
-  // passes run; a batch that falls back to the push path joins the chain first
-  // and has churn_ring replay its ring slots. A replay (from epoch 0 up to the
-  // falling-back batch's last epoch) takes the ring and the mesh state back
-  // below the prepared batch's last epoch ah.h1: the prepared batch is then
-  // dropped and prepares in line after the push path's run, as a batch without
-  // a chain ahead does (the seeds and the push path read the ring's offline
-  // bits, so a prepared batch is only good while the ring holds its epochs).
-  constexpr uint64_t AH_MARK = 16, AH_LEAD = 192, AH_SLICE = 64;
-  struct Ahead {
-    bool on = false, joined = false;
-    uint64_t i0 = 0, i1 = 0, h1 = 0;
-    ChnPrep cp;
-    EvRun* run = nullptr;
-    hipEvent_t ready = nullptr;
-    std::vector<hipEvent_t> marks;  // ring of events every AH_MARK epochs on the chain stream
-    uint64_t mark_n = 0, done_h = 0, enq_h = 0;
-  } ah;
-  struct AheadFree {
-    Ahead& ah;
-    ~AheadFree() {
-      if (ah.run) chain_free(ah.run);
-      if (ah.ready) (void)hipEventDestroy(ah.ready);
-      for (auto e : ah.marks) (void)hipEventDestroy(e);
-    }
-  } ah_free{ah};
-  std::vector<uint64_t> q0a(Bmax), r0a(Bmax);
-  static const bool dbg_ah = getenv("GS_DEBUG_AHEAD") != nullptr;
-  auto ah_enqueue_end = [&] {  // every epoch is enqueued: the rest of the tables, then `ready`
-    if (dbg_ah) fprintf(stderr, "[ah] batch %llu: chain enqueued (%llu epochs)\n", (unsigned long long)ah.i0,
-                        (unsigned long long)ah.enq_h);
-    chain_free(ah.run);
-    ah.run = nullptr;
-    chn_end(c, ah.cp, c.chain_pipe);
-    if (!ah.ready) GS_HIP(hipEventCreateWithFlags(&ah.ready, hipEventDisableTiming));
-    GS_HIP(hipEventRecord(ah.ready, c.chain_pipe));
-  };
-  auto ah_pump = [&](bool all) {  // more of the chain, keeping at most AH_LEAD epochs in flight
-    if (!ah.on || !ah.run) return;
-    while (ah.run) {
-      if (!all) {
-        while (ah.mark_n && ah.done_h + AH_MARK <= ah.enq_h) {  // the oldest outstanding mark
-          const uint64_t k = ah.done_h / AH_MARK + 1;  // mark k: after epoch k * AH_MARK of the run
-          if (k > ah.mark_n) break;
-          if (hipEventQuery(ah.marks[(k - 1) % ah.marks.size()]) != hipSuccess) break;
-          ah.done_h = k * AH_MARK;
-        }
-        if (ah.enq_h >= ah.done_h + AH_LEAD) return;
-      }
-      const uint64_t n = all ? ~0ull : std::min<uint64_t>(AH_SLICE, ah.done_h + AH_LEAD - ah.enq_h);
-      for (uint64_t k = 0; k < n && ah.run; k++) {
-        const bool fin = chain_advance(c, *ah.run, 1);
-        ah.enq_h++;
-        if (ah.enq_h % AH_MARK == 0) {
-          if (ah.marks.size() < 2 * AH_LEAD / AH_MARK + 2) {
-            hipEvent_t e;
-            GS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            ah.marks.push_back(e);
-          }
-          ah.mark_n = ah.enq_h / AH_MARK;
-          GS_HIP(hipEventRecord(ah.marks[(ah.mark_n - 1) % ah.marks.size()], c.chain_pipe));
-        }
-        if (fin) ah_enqueue_end();
-      }
-      if (!all) return;
-    }
-  };
-  auto ah_join = [&] {  // the prepared batch's tables before the main stream's next work
-    if (!ah.on || ah.joined) return;
-    ah_pump(true);
-    GS_HIP(hipStreamWaitEvent(c.stream, ah.ready, 0));
-    ah.joined = true;
-    if (dbg_ah) fprintf(stderr, "[ah] batch %llu: joined\n", (unsigned long long)ah.i0);
-  };
-  auto ah_start = [&](uint64_t n0) {
-    if (!pipe_on || ah.on || n0 >= n_msgs) return;
-    uint64_t hl = 0, hh = 0;
-    const uint64_t n1 = form(n0, hl, hh);
-    const Batch b2 = setup_batch(c, sched, n0, n1, false);
-    const uint64_t hb = c.cfg.heartbeat_ns, ph = c.cfg.hb_phase_ns;
-    for (uint32_t q = 0; q < b2.B; q++) {
-      q0a[q] = ep[n0 + q];
-      r0a[q] = b2.tpub[q] - ph - q0a[q] * hb;
-    }
-    const uint64_t h1 = hh + c.cfg.churn_horizon;
-    if (!chn_decide(b2, r0a.data(), hl, hh) || h1 <= c.churn_state) return;
-    const uint32_t par = c.ct_par ^ 1u;
-    // the chain overwrites ring slots: after every reader of this batch's slots on the main stream
-    if (!ah.ready) GS_HIP(hipEventCreateWithFlags(&ah.ready, hipEventDisableTiming));
-    GS_HIP(hipEventRecord(ah.ready, c.stream));
-    GS_HIP(hipStreamWaitEvent(c.chain_pipe, ah.ready, 0));
-    chn_begin(c, ah.cp, par, c.chain_pipe, hl, (uint32_t)(h1 - hl + 1), q0a.data(), sched + n0, b2.B, b2.FP);
-    ah.run = chain_begin(c, h1, c.chain_pipe, [&](uint64_t h) { chn_chunks(c, ah.cp, h, false); });
-    if (!ah.run) return;  // (not a plain continuation of the ring: the batch prepares in line)
-    c.ct_par = par;
-    ah.on = true;
-    ah.joined = false;
-    ah.i0 = n0;
-    ah.i1 = n1;
-    ah.h1 = h1;
-    ah.mark_n = ah.done_h = ah.enq_h = 0;
-    if (dbg_ah)
-      fprintf(stderr, "[ah] batch %llu..%llu: chain to epoch %llu (state %llu), tables %u\n", (unsigned long long)n0,
-              (unsigned long long)n1, (unsigned long long)h1, (unsigned long long)c.churn_state, par);
-    ah_pump(false);
-  };
-  uint64_t i0 = 0;
-  for (c.run_batch = 0; i0 < n_msgs; c.run_batch++) {
-    if (i0 >= slice_skip) {
-      uint64_t ie = 0;
-      if (try_slices(i0, ie)) {
-        i0 = ie;
-        continue;
-      }
-    }
-    uint64_t h_lo = 0, h_hi = 0;  // churn: publish epochs of the batch
-    const uint64_t i1 = form(i0, h_lo, h_hi);
-    const Batch b = setup_batch(c, sched, i0, i1);
-    const uint32_t FP = b.FP;
-    bool chn = false;  // this batch runs on the churn list pass
-    ChnPrep cp;
-    if (churn) {
-      const uint64_t hb = c.cfg.heartbeat_ns, ph = c.cfg.hb_phase_ns;
-      for (uint32_t q = 0; q < b.B; q++) {
-        q0v[q] = ep[i0 + q];
-        r0v[q] = b.tpub[q] - ph - q0v[q] * hb;
-      }
-      chn = chn_decide(b, r0v.data(), h_lo, h_hi);
-      if (ah.on && !(chn && ah.i0 == i0 && ah.i1 == i1)) {  // (not expected: batches form the same way)
-        ah_join();
-        ah.on = false;
-      }
-      if (ah.on) {  // this batch's chain and tables ran ahead beside the last batch's passes
-        ah_join();
-        cp = ah.cp;
-        ah.on = false;
-      } else {
-        c.ring_in_defer = chn;  // the push path's inverse IHAVE lists are not needed
-        c.ring_ell_defer = chn;  // nor the ELL snapshots (the pass reads the mask ring)
-        if (chn) {
-          c.ct_par ^= 1u;
-          chn_begin(c, cp, c.ct_par, s, h_lo, (uint32_t)(h_hi + c.cfg.churn_horizon - h_lo + 1), q0v.data(), sched + i0,
-                    b.B, b.FP);
-          cp.s = nullptr;  // (the chunk events go where churn_ring runs the chain)
-          c.epoch_hook = [&](uint64_t h) { chn_chunks(c, cp, h, false); };
-        }
-        try {
-          churn_ring(c, h_lo, h_hi + c.cfg.churn_horizon);
-        } catch (...) {
-          c.epoch_hook = nullptr;
-          c.ring_in_defer = false;
-          c.ring_ell_defer = false;
-          throw;
-        }
-        c.epoch_hook = nullptr;
-        c.ring_in_defer = false;
-        c.ring_ell_defer = false;
-        // readers of the ELL snapshots beside the list pass: seeds to the mesh (no flood
-        // publish), the per-peer traffic pass, the GS_DEBUG_CHN check
-        if (chn && (!c.cfg.flood_publish || c.traffic || getenv("GS_DEBUG_CHN")))
-          ensure_ring_ell(c, h_lo, h_hi + c.cfg.churn_horizon);
-        //  a batch for the push path may overlap the last epochs of an
-        // earlier churn list-pass batch, which skipped their ELL snapshots and
-        // inverse IHAVE lists: rebuild those slots (tag-checked: free when current)
-        if (!chn) {
-          ensure_ring_ell(c, h_lo, h_hi + c.cfg.churn_horizon);
-          if (gossip) ensure_in_lists(c, h_lo, h_hi + c.cfg.churn_horizon);
-        }
-        if (chn) chn_end(c, cp);
-      }
-      c.d_q0.alloc(Bmax);
-      c.d_r0.alloc(Bmax);
-      GS_HIP(hipMemcpyAsync(c.d_q0.p, q0v.data(), b.B * 8, hipMemcpyHostToDevice, s));
-      GS_HIP(hipMemcpyAsync(c.d_r0.p, r0v.data(), b.B * 8, hipMemcpyHostToDevice, s));
-      GS_HIP(hipStreamSynchronize(s));
-    }
-    const uint32_t B = b.B, L = b.L;
-    if (gossip) {  // heartbeats at hb_phase + h*hb: first one at or after each t_pub
-      const uint64_t hb = c.cfg.heartbeat_ns, ph = c.cfg.hb_phase_ns;
-      for (uint32_t q = 0; q < B; q++) {
-        const uint64_t tp = b.tpub[q];
-        const uint64_t h0 = tp <= ph ? 0 : (tp - ph + hb - 1) / hb;
-        rel0[q] = ph + h0 * hb - tp;
-        habs0[q] = h0;
-      }
-      c.d_rel0.alloc(Bmax);
-      c.d_habs0.alloc(Bmax);
-      GS_HIP(hipMemcpyAsync(c.d_rel0.p, rel0.data(), B * 8, hipMemcpyHostToDevice, s));
-      GS_HIP(hipMemcpyAsync(c.d_habs0.p, habs0.data(), B * 8, hipMemcpyHostToDevice, s));
-      g0 = INF64;
-      if (churn) {  // per message: gossip can spread it (publisher online at t_pub, a heartbeat in its lifetime)
-        for (uint32_t q = 0; q < B; q++) {
-          malive[q] = habs0[q] <= q0v[q] + c.cfg.churn_horizon &&
-                      !offline_draw(c.cfg.seed, c.cfg.churn_ppm, c.cfg.churn_down, sched[i0 + q].publisher, q0v[q]);
-          g0 = std::min(g0, rel0[q]);
-        }
-        uint64_t lmin = INF64;
-        for (uint64_t l : c.lat_ns) lmin = std::min(lmin, l);
-        g0 += lmin;
-        c.d_malive.alloc(Bmax);
-        GS_HIP(hipMemcpyAsync(c.d_malive.p, malive.data(), B, hipMemcpyHostToDevice, s));
-      }
-      GS_HIP(hipStreamSynchronize(s));  // rel0 / habs0 host vectors are rewritten by the next batch
-    }
-    const uint64_t total = (uint64_t)N * L;
-    auto reset = [&](uint32_t v, bool with_gossip, bool dense_keys = true) {  // fresh keys and bucket state
-      c.keys_log = c.keys_none = false;
-      if (dense_keys) GS_HIP(hipMemsetAsync(c.d_keys.p, 0xFF, total * 8, s));  // the list pull path needs none
-      if (FP > 1) GS_HIP(hipMemsetAsync(c.d_busy.p, 0, (size_t)N * B * 8, s));
-      if (v & 32) return;
-      if (v & 2) GS_HIP(hipMemsetAsync(c.d_meta.p, 0, (total + 63) / 64 * sizeof(TileMeta), s));
-      if (v & 12) GS_HIP(hipMemsetAsync(c.d_fbits.p, 0, (total + 63) / 64 * 8, s));
-      if ((v & 10) == 10) {  // split + tile skip: tmin 0 forces every tile's first scan
-        c.d_tmin.alloc(max_tiles);
-        c.d_touched.alloc(max_tiles);
-        GS_HIP(hipMemsetAsync(c.d_tmin.p, 0, (total + 63) / 64 * 8, s));
-        GS_HIP(hipMemsetAsync(c.d_touched.p, 0, (total + 63) / 64, s));
-        if (with_gossip) {
-          c.d_tgmin.alloc(max_tiles);
-          c.d_tnf.alloc(max_tiles);
-          c.d_tstamp.alloc(max_tiles);
-          GS_HIP(hipMemsetAsync(c.d_tstamp.p, 0, (total + 63) / 64 * 4, s));
-        }
-      }
-      GS_HIP(hipMemsetAsync(c.d_ctrl.p, 0xFF, 4 * 8, s));
-      // with gossip the first bucket is [0, Delta): the publisher's own IHAVEs
-      // can land before the first eager arrival
-      if (with_gossip) GS_HIP(hipMemsetAsync(c.d_ctrl.p, 0, 8, s));
-    };
-    // One batch on the push path: k_seed, then bucket launches in chunks of 8
-    // until the ctrl word of the next bucket is empty.
-    auto push_run = [&](uint32_t v, bool with_gossip) {
-      reset(v, with_gossip);
-      launch_seed(c, b, 0, N);
-      RelaxArgs ra = relax_args(c, b, with_gossip);
-      if (ra.ring_in) {
-        ra.malive = c.d_malive.p;
-        ra.g0 = g0;
-      }
-      ra.busy = c.d_busy.p;
-      ra.meta = reinterpret_cast<TileMeta*>(c.d_meta.p);
-      ra.fbits = c.d_fbits.p;
-      ra.tmin = c.d_tmin.p;
-      ra.touched = c.d_touched.p;
-      ra.ctrl = c.d_ctrl.p;
-      ra.counters = c.d_counters.p; ra.delta = b.delta;
-      const uint64_t need = (total + TB - 1) / TB;
-      const unsigned grid = (unsigned)std::min<uint64_t>(need, (uint64_t)dev_cus * SPLIT_BLOCKS_PER_CU);
-      if (v & 8) {  // frontier segments: one per scan wave
-        const uint64_t nwaves = (uint64_t)grid * (TB / 64), ntiles = (total + 63) / 64;
-        // tiles one scan wave can visit: groups of 64 with tile skip (k_scan), single tiles without
-        const uint64_t gt = (v & 2) ? 64 : 1;
-        const uint64_t wave_tiles = ((ntiles + gt - 1) / gt + nwaves - 1) / nwaves * gt;
-        ra.seg_cap = (uint32_t)(wave_tiles * (64 / FP));
-        c.d_fr_idx.alloc(nwaves * ra.seg_cap);
-        if (FP == 1) c.d_fr_key.alloc(nwaves * ra.seg_cap);
-        c.d_fr_cnt.alloc(nwaves);
-        ra.fr_idx = c.d_fr_idx.p;
-        ra.fr_key = c.d_fr_key.p;
-        ra.fr_cnt = c.d_fr_cnt.p;
-        if (with_gossip) {  // gossip list: per-lane entries, one segment per scan wave
-          ra.gl_cap = (uint32_t)(wave_tiles * 64);
-          c.d_gl_idx.alloc(nwaves * ra.gl_cap);
-          c.d_gl_cnt.alloc(nwaves);
-          c.d_nonfinal.alloc(3);
-          GS_HIP(hipMemsetAsync(c.d_nonfinal.p, 0, 3 * 8, s));
-          ra.gl_idx = c.d_gl_idx.p;
-          ra.gl_cnt = c.d_gl_cnt.p;
-          if (ra.ring_in) {
-            c.d_gl_key.alloc(nwaves * ra.gl_cap);
-            ra.gl_key = c.d_gl_key.p;
-            // holder list (a lane is finalised once) and per-launch marks
-            c.d_hl_idx.alloc(total);
-            c.d_hl_key.alloc(total);
-            c.d_hl_cnt.alloc(1);
-            c.d_hl_mark.alloc(2 * (size_t)HL_LAUNCHES);
-            c.d_hwin.alloc(total);
-            GS_HIP(hipMemsetAsync(c.d_hwin.p, 0xFF, total, s));
-            ra.hwin = c.d_hwin.p;
-            c.d_hs_idx.alloc(nwaves * ra.gl_cap);
-            c.d_hs_key.alloc(nwaves * ra.gl_cap);
-            c.d_hl_min.alloc(3);
-            GS_HIP(hipMemsetAsync(c.d_hl_cnt.p, 0, 8, s));
-            GS_HIP(hipMemsetAsync(c.d_hl_min.p, 0xFF, 3 * 8, s));
-            ra.hs_idx = c.d_hs_idx.p;
-            ra.hs_key = c.d_hs_key.p;
-            ra.hl_min = c.d_hl_min.p;
-            ra.hl_idx = c.d_hl_idx.p;
-            ra.hl_key = c.d_hl_key.p;
-            ra.hl_cnt = (unsigned long long*)c.d_hl_cnt.p;
-            ra.hl_lo = c.d_hl_mark.p;
-            ra.hl_end = c.d_hl_mark.p + HL_LAUNCHES;
-          }
-          ra.nonfinal = c.d_nonfinal.p;
-          if ((v & 10) == 10) {
-            ra.tgmin = c.d_tgmin.p;
-            ra.tnf = c.d_tnf.p;
-            ra.tstamp = c.d_tstamp.p;
-          }
-        }
-      }
-      uint32_t launch = 0;
-      const uint32_t chunk = 8;
-      for (;;) {
-        if (ra.hl_idx && launch + chunk > HL_LAUNCHES)
-          c.fail(GS_EUNSUPPORTED, "churn + lazy gossip batch needs more than 65536 buckets");
-        for (uint32_t q = 0; q < chunk; q++) {
-          ra.launch = launch++;
-          if (c.timing) {  // (start, scan end, end) per bucket
-            GS_HIP(hipEventRecord(ev(n_ev), s));
-            const hipEvent_t mid = ev(n_ev + 1);
-            if (v & 8) relax_dispatch(FP, v, ra, grid, s, mid);
-            else {
-              relax_dispatch(FP, v, ra, grid, s);
-              GS_HIP(hipEventRecord(mid, s));
-            }
-            GS_HIP(hipEventRecord(ev(n_ev + 2), s));
-            n_ev += 3;
-          } else {
-            relax_dispatch(FP, v, ra, grid, s);
-          }
-        }
-        GS_HIP(hipGetLastError());
-        GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_ctrl.p, 3 * 8, hipMemcpyDeviceToHost, s));
-        GS_HIP(hipStreamSynchronize(s));
-        if (c.h_pinned[launch % 3] == INF64) break;
-      }
-      c.stats.relax_launches += launch;
-    };
-    // Lazy gossip on a frozen mesh: run eager forwarding first (the pull pass,
-    // or the push path without gossip when IDONTWANT needs it) and keep it if
-    // the batch proves gossip a no-op; otherwise discard its counters and run
-    // the push path with gossip. Under churn some peers never
-    // complete, so the proof cannot hold and gossip runs directly.
-    const bool idw_b = c.cfg.idontwant && b.payload >= c.cfg.idontwant;  // IDONTWANT active in this batch
-    // IDONTWANT on the list pass: windows no wider than the smallest latency, so
-    // that a neighbour's key final in the same window as the sender's can never
-    // pass the test t_y + lat(y -> u) <= t_u (the sender cannot see it yet);
-    // keys of earlier windows are final and stored before the pass starts
-    Batch bw = b;
-    if (idw_b) bw.delta = std::min(b.delta, b.lat_min);
-    // fragmented IDONTWANT batches (rows of fragment groups, each lane tested on its
-    // own) wherever fragmented rows run at all (bit 128); GS_IDW_FRAG_LIST=0 keeps
-    // them on the push path (A/B, per batch). With colliding fragments (defect D8)
-    // only lane 0 of a group is ever final, as without IDONTWANT.
-    const bool idw_frag = (variant & 128) && !env_off("GS_IDW_FRAG_LIST");
-    const bool pull_ok = pull_any && bw.delta >= pull_grain(b.tshift) &&
-                         (!idw_b || ((variant & 64) && (b.FP == 1 || idw_frag)));
-    // Lazy gossip inside the list pass (GOS, gs_lpull_kernel.h): rows with or
-    // without IDONTWANT (fragment groups too: every fragment is gossiped on its own at its
-    // message's heartbeats, as the oracle's sched_gossip) on the frozen mesh, every message's heartbeats
-    // the same time after its publish (lockstep), CSR rows narrow enough for a
-    // 58-bit target mask, windows no wider than the smallest latency (an IHAVE
-    // never shares a window with its heartbeat) and heartbeats farther apart
-    // than an IHAVE travels. GS_GOSSIP_LIST=0 keeps such batches on the eager
-    // pass + no-op proof, with the push path behind it.
-    bool lockstep = gossip && B > 0;
-    for (uint32_t q = 1; q < B && lockstep; q++) lockstep = rel0[q] == rel0[0];
-    Batch bg = b;
-    bg.delta = std::min(b.delta, b.lat_min);
-    const uint64_t ggr = pull_grain(b.tshift);
-    const bool glp = gossip && !churn && pull_ok && (b.FP == 1 || (variant & 128)) && (variant & 64) && lockstep &&
-                     !env_off("GS_GOSSIP_LIST") && c.max_degree <= GSE_HOPS && bg.delta >= ggr &&
-                     c.cfg.heartbeat_ns > b.lat_max + bg.delta;
-    bool glp_tried = false;
-    auto run_glp = [&]() -> bool {
-      glp_tried = true;
-      uint32_t lb = 0;
-      const uint32_t K = lpull_ring(c, bg, bg.delta / ggr * ggr, &lb, true);
-      if (!K) return false;
-      reset(variant, false, idw_b);  // IDONTWANT: dense INF keys (the finals stay dense rows)
-      const GosRun gr{rel0[0], c.cfg.heartbeat_ns};
-      const SinkWants sw = sink_wants(sink);
-      const bool dense = sw.rows() || sw.summary || c.traffic || getenv("GS_LPULL_DENSE");
-      const uint64_t iw0 = read_counter(c, C_GOSSIP);
-      if (!run_lpull_batch(c, bg, K, lb, ev, n_ev, dev_cus, dense, idw_b, &gr)) return false;
-      c.stats.gossip_list_batches++;
-      // GLP_QUIET batches in a row whose gossip sent no IWANT: the next one tries the
-      // eager pass and its no-op proof first again (glp_prefer was never
-      // cleared). Not after one: batches alternating with and without IWANTs (a
-      // heartbeat late in the dissemination) would pay a failed proof every other batch.
-      if (read_counter(c, C_GOSSIP) != iw0) c.glp_quiet = 0;
-      else if (++c.glp_quiet >= GLP_QUIET) c.glp_prefer = false;
-      if (c.traffic) launch_traffic(c, b);
-      launch_complete(c, b, 0, N, sink, i0);
-      return true;
-    };
-    bool done = false;
-    NoLog nl;  // the eager batch ran the no-log list pass (set below)
-    if (chn) {  // churn on the list pass; a list overflow falls back to the push path
-      uint32_t lb = 0;
-      Batch bc = b;
-      if (gossip) bc.delta = std::min(b.delta, b.lat_min);
-      const uint64_t grain = pull_grain(b.tshift);
-      const uint32_t K = lpull_ring(c, bc, bc.delta / grain * grain, &lb, gossip, true);
-      if (K) {
-        reset(variant, false, false);
-        const GosRun gr{rel0[0], c.cfg.heartbeat_ns};
-        const ChnRun cr{h_lo, r0v[0], (uint32_t)(h_hi + c.cfg.churn_horizon - h_lo + 1),
-                        gossip ? (uint32_t)(habs0[0] - q0v[0]) : 0u, cp.par};
-        const SinkWants sw = sink_wants(sink);
-        const bool dense = sw.rows() || sw.summary || c.traffic || getenv("GS_LPULL_DENSE");
-        // the next batch's chain beside these passes, from the first pass group on:
-        // the seeds (k_seed reads this batch's offline bits in the ring) are
-        // enqueued by then, and the chain's stream waits for them
-        bool ah_tried = false;
-        if (pipe_on) c.pass_poll = [&] {
-          if (!ah_tried) {
-            ah_tried = true;
-            ah_start(i1);
-          } else {
-            ah_pump(false);
-          }
-        };
-        struct PollOff {
-          Ctx& c;
-          ~PollOff() { c.pass_poll = nullptr; }
-        } poll_off{c};
-        if (run_lpull_batch(c, bc, K, lb, ev, n_ev, dev_cus, dense, false, gossip ? &gr : nullptr, &cr)) {
-          if (gossip) c.stats.gossip_list_batches++;
-          if (c.traffic) launch_traffic(c, b);
-          launch_complete(c, b, 0, N, sink, i0);
-          done = true;
-        }
-      }
-      if (!done && getenv("GS_REQUIRE_LPULL")) c.fail(GS_EUNSUPPORTED, "churn list pass cannot take this batch (GS_REQUIRE_LPULL)");
-      if (!done) {  // the push path reads the ring: a chain ahead (of this batch or for the next one)
-        ah_join();    // may have run past or overwritten this batch's slots, or a replay moved the ring
-        churn_ring(c, h_lo, h_hi + c.cfg.churn_horizon);  // (no epochs when current; else runs / replays them)
-        // a replay ended at this batch's last epoch: the ring slots of the prepared batch's later
-        // epochs (its seeds read their offline bits) hold older epochs again and the mesh state is
-        // behind its tables. The prepared batch is dropped and prepares in line (chn_begin into the
-        // other table set, which this batch's list pass has left; churn_ring runs the epochs again).
-        // The join above enqueued the whole chain and churn_ring waited for its stream.
-        if (ah.on && c.churn_state < ah.h1) {
-          if (dbg_ah)
-            fprintf(stderr, "[ah] batch %llu: dropped (the fallback's replay left the ring at epoch %llu of %llu)\n",
-                    (unsigned long long)ah.i0, (unsigned long long)c.churn_state, (unsigned long long)ah.h1);
-          ah.on = false;
-        }
-      }
-      if (!done) ensure_ring_ell(c, h_lo, h_hi + c.cfg.churn_horizon);  // the push path reads the ELL ring
-      if (!done && gossip) ensure_in_lists(c, h_lo, h_hi + c.cfg.churn_horizon);
-    }
-    if (glp && c.glp_prefer) done = run_glp();
-    if (!done && (pull_ok || (gossip && !churn))) {
-      if (gossip) GS_HIP(hipMemcpyAsync(c.d_cnt_save.p, c.d_counters.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
-      if (pull_ok) {
-        const uint64_t grain = pull_grain(b.tshift);
-        uint32_t lb = 0;
-        // list path for single-fragment batches; fragmented ones (FP > 1) with
-        // bit 128 (the default)
-        const bool lp = (variant & 64) && (b.FP == 1 || (variant & 128));
-        const uint32_t K = lp ? lpull_ring(c, bw, bw.delta / grain * grain, &lb) : 0u;
-        reset(variant, false, K == 0 || idw_b);  // IDONTWANT: dense INF keys
-        if (lp && !K && getenv("GS_REQUIRE_LPULL"))  // test knob: no silent k_pull fallback
-          c.fail(GS_EUNSUPPORTED, "list pull path cannot take this batch (GS_REQUIRE_LPULL)");
-        // GS_LPULL_DENSE (diagnostic): dense rows + k_complete, whose known key
-        // stream calibrates the PMC read factor (scripts/pmc_summary.py);
-        // IDONTWANT batches keep their final keys dense all along
-        const SinkWants sw = sink_wants(sink);
-        const bool dense = !idw_b && (sw.rows() || sw.summary || c.traffic || getenv("GS_LPULL_DENSE"));
-        // No log (the passes complete the batch) exactly when nothing will read a per-message
-        // value: no sink wants, no traffic pass, rows of single-fragment lanes on the frozen
-        // mesh without IDONTWANT, and with lazy gossip a lockstep batch, whose no-op proof
-        // needs the batch's deliveries and latest final time only (batch_sums). The passes'
-        // 32-bit ms need every final time below 2^38 ns: checked on the batch's latest final
-        // time after its passes (NoLog::inexact). GS_LPULL_SUM=0 (A/B, per batch): the log and k_lsum.
-        nl.on = K && !dense && !sw.lat && !idw_b && !churn && b.FP == 1 && (!gossip || lockstep) &&
-                !env_off("GS_LPULL_SUM");
-        bool lp_ok =
-            K && run_lpull_batch(c, bw, K, lb, ev, n_ev, dev_cus, dense, idw_b, nullptr, nullptr, nullptr, &nl);
-        if (!lp_ok && nl.inexact) {  // the same pass again with its log (k_lsum's 64-bit ms)
-          nl = NoLog{};
-          lp_ok = run_lpull_batch(c, bw, K, lb, ev, n_ev, dev_cus, dense, idw_b);
-        }
-        if (!lp_ok) {
-          nl.on = false;
-          if (K && getenv("GS_REQUIRE_LPULL")) c.fail(GS_EUNSUPPORTED, "list pull overflow (GS_REQUIRE_LPULL)");
-          if (idw_b) {  // k_pull has no IDONTWANT: the push path takes the batch
-            push_run(variant & ~32u, false);
-          } else {  // a candidate list overflowed (or no ring fits): this batch runs on k_pull
-            if (K) reset(variant, false);
-            run_pull_batch(c, b, ev, n_ev, dev_cus);
-          }
-        }
-      } else {
-        push_run(variant & ~32u, false);
-      }
-      if (!gossip) {
-        if (c.traffic) launch_traffic(c, b);
-        if (!nl.on) launch_complete(c, b, 0, N, sink, i0);  // (a no-log batch: the passes completed it)
-        done = true;
-      } else {  // keep the eager result only if gossip provably changes nothing
-        const SinkWants sw = sink_wants(sink);
-        // a lockstep batch (one rel0): a message has at most N - 1 deliveries, so the batch's
-        // total is reached only when none is undelivered, and the largest of the messages'
-        // latest times is the batch's; the per-message test is then a test of these two
-        bool noop;
-        if (nl.on) {  // the two values came with the last pass group's control words
-          noop = nl.deliv == (uint64_t)B * (N - 1) && nl.tmax < rel0[0] + b.lat_min;
-        } else {
-          const bool bsum = batch_sums(c, b, true, sw.lat, 1, lockstep);
-          run_complete(c, b, 0, N, true, sw.summary, sw.rows() || sw.summary, sw.lat, 0, nullptr, nullptr, 1, lockstep);
-          std::vector<uint64_t> ms(bsum ? 2 : (size_t)B * MS_COLS);
-          GS_HIP(hipMemcpyAsync(ms.data(), c.d_mstat.p, ms.size() * 8, hipMemcpyDeviceToHost, s));
-          GS_HIP(hipStreamSynchronize(s));
-          noop = bsum ? ms[0] == (uint64_t)B * (N - 1) && ms[1] < rel0[0] + b.lat_min : gossip_noop(b, ms.data(), rel0);
-        }
-        if (noop) {
-          if (c.traffic) launch_traffic(c, b);
-          deliver(c, b, 0, N, sink, i0);
-          c.stats.gossip_noop_msgs += B;
-          done = true;
-        } else {  // gossip can change this batch: discard the eager run's counters
-          GS_HIP(hipMemcpyAsync(c.d_counters.p, c.d_cnt_save.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
-          c.stats.gossip_fallback_batches++;
-          if (glp && !glp_tried) {  // re-run with the gossip inside the passes; the context's
-            c.glp_prefer = true;      // later batches go there directly (no eager run first)
-            c.glp_quiet = 0;
-            done = run_glp();
-          }
-        }
-      }
-    }
-    if (!done) {
-      if (getenv("GS_REQUIRE_LPULL")) c.fail(GS_EUNSUPPORTED, "the push path would take this batch (GS_REQUIRE_LPULL)");
-      if (gossip && !lanes32)
-        c.fail(GS_EUNSUPPORTED, "lazy gossip changes this batch and the push path needs "
-                                "peers*batch*FP < 2^32: use a smaller batch");
-      push_run(pvariant, gossip);
-      if (c.traffic) launch_traffic(c, b);
-      launch_complete(c, b, 0, N, sink, i0);
-    }
-    c.stats.messages += B;
-    c.stats.batches++;
-    i0 = i1;
-  }
-  lat_flush(c);  // the last batch's latencies
-  if (c.timing) GS_HIP(hipEventRecord(ev(1), s));
-  collect_stats(c);
-  if (c.timing) {
-    double scan = 0, front = 0;
-    for (size_t q = 2; q + 2 < n_ev; q += 3) {
-      float x = 0, y = 0;
-      GS_HIP(hipEventElapsedTime(&x, c.ev_pool[q], c.ev_pool[q + 1]));
-      GS_HIP(hipEventElapsedTime(&y, c.ev_pool[q + 1], c.ev_pool[q + 2]));
-      scan += x;
-      front += y;
-    }
-    c.stats.relax_ms += scan + front;
-    c.stats.scan_ms += scan;
-    c.stats.frontier_ms += front;
-    float rm = 0;
-    GS_HIP(hipEventElapsedTime(&rm, c.ev_pool[0], c.ev_pool[1]));
-    c.stats.run_ms += rm;
-  }
-}
 
 #include "gs_part.h"
 

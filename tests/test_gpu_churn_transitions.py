@@ -1,7 +1,7 @@
 """Churn batch path transitions against the CPU oracle.
 
 A churn run carries the epoch ring, the table-set parity, the saved counters
-and the chain ahead (gs_relax.hip ChnAhead) from one batch to the next, and a
+and the chain ahead (gs_run.h Ahead) from one batch to the next, and a
 batch takes one of three paths:
 
   L  the churn list pass;

@@ -252,3 +252,26 @@ def test_gossip_in_list_pass_idontwant(phase_ms):
     st = sim.stats()
     assert st["gossip_iwant"] > 0
     assert st["gossip_fallback_batches"] <= 1 and st["gossip_list_batches"] >= 3
+
+
+def test_quiet_batches_return_to_the_eager_pass(monkeypatch):
+    """The path choice a failed no-op proof teaches is unlearnt again: batch 0
+    has a heartbeat 120 ms after its publishes (IWANTs: its eager proof fails,
+    one fallback, and the context prefers the in-pass gossip); batches 1..8 have
+    theirs 920 ms after (everyone holds the message by then: no IWANT) and run
+    their gossip inside the passes directly; after these GLP_QUIET = 8 quiet
+    batches batch 9 tries the eager pass first again and its proof holds.
+    (10 batches of 8 at 600 peers: the rule needs 1 + 8 + 1.)"""
+    monkeypatch.setenv("GS_SLICES", "0")
+    monkeypatch.setenv("GS_REQUIRE_LPULL", "1")
+    N, B = 600, 8
+    t = T0 + np.arange(10 * B, dtype=np.uint64) * np.uint64(HB)
+    t[B:] += np.uint64(200_000_000)
+    p = oracle.params(peers=N, seed=230, hb_phase_ns=_phase(120))
+    sim, _ = compare(p, 5, LINKS, (t, (6 + np.arange(10 * B)) % N, np.full(10 * B, 15000)), batch=B)
+    st = sim.stats()
+    print({k: st[k] for k in ("batches", "gossip_iwant", "gossip_fallback_batches", "gossip_list_batches",
+                              "gossip_noop_msgs", "list_pull_batches")})
+    assert st["batches"] == 10 and st["gossip_iwant"] > 0
+    assert st["gossip_fallback_batches"] == 1 and st["gossip_list_batches"] == 9
+    assert st["gossip_noop_msgs"] == B

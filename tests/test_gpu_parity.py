@@ -628,7 +628,7 @@ def test_churn_list_pass_chain_ahead(monkeypatch, gossip, pipe):
     """Churn batches back to back on the list pass: with GS_CHN_PIPE on (the
     default on a 256-CU MI355X), batch k+1's epoch chain and tables are
     enqueued on the chain's XCD while batch k's passes run on the others
-    (gs_relax.hip ChnAhead). Bit-exact against the oracle over 4 batches."""
+    (gs_run.h Ahead). Bit-exact against the oracle over 4 batches."""
     monkeypatch.setenv("GS_CHN_PIPE", pipe)
     monkeypatch.setenv("GS_REQUIRE_LPULL", "1")
     hb = 400_000_000

@@ -1,11 +1,11 @@
-"""Batch slices (gs_relax.hip try_slices / run_lpull_batch's Slices): several
+"""Batch slices (gs_run.h Run::try_slices / run_lpull_batch's Slices): several
 full batches of one shape on a small graph run as ONE list pass over copies of
 the graph (slice j's rows are j * N + peer). The results must be those of the
 same batches run one at a time (GS_SLICES=0) and of the CPU oracle, for every
 way a run hands results out (rows, streamed blocks, latency stream, summaries,
 device-resident counters), with single- and multi-fragment rows and with lazy
 gossip (the eager pass's no-op proof per slice, and a phase where the proof
-fails and the group is re-run as single batches).
+fails and the group is re-run with the gossip inside its passes).
 
 Reference: config #2 (BASELINE.json, shadow/README.md:57: 10k peers,
 FRAGMENTS=8, 1000 messages); main.rs:101-143 / 228-235 for the rules the
@@ -97,8 +97,8 @@ def test_slices_gossip_phase_falls_back_exactly(monkeypatch):
     p = oracle.params(peers=1200, seed=330, hb_phase_ns=(T0 + 120_000_000) % HB)
     sim, _ = compare(p, 5, LINKS, _sched(32, 1200), batch=8)
     st = sim.stats()
-    # the first single batch's eager pass fails its proof (the group's counts nothing), then every
-    # batch runs its gossip inside the list pass
+    # the group's eager pass fails its proof (one fallback), then the group runs its gossip
+    # inside its passes
     assert st["gossip_iwant"] > 0 and st["batches"] == 4
     assert st["gossip_fallback_batches"] == 1 and st["gossip_list_batches"] == 4
 
@@ -160,3 +160,53 @@ def test_slices_gossip_active_against_oracle(monkeypatch):
     sim, _ = compare(p, 5, LINKS, _sched(40, 1100), batch=8)
     st = sim.stats()
     assert st["gossip_iwant"] > 0 and st["gossip_list_batches"] == 5
+
+
+def test_slices_failed_proof_reruns_the_group_in_pass(monkeypatch):
+    """The group whose eager no-op proof fails runs again as a group, with the
+    gossip inside its passes, not as single batches: against the oracle both
+    ways, the same fallback and in-pass counts, and fewer than half the window
+    passes. (Passes of one batch: P1 eager, P2 >= P1 with the in-pass gossip's
+    narrower windows; a group's pass count is a batch's. Sliced P1 + P2, single
+    batches P1 + 4 * P2 > 2 * (P1 + P2).)"""
+    p = oracle.params(peers=1200, seed=330, hb_phase_ns=(T0 + 120_000_000) % HB)
+    sched = _sched(32, 1200)
+    ref = oracle.simulate(p, 5, LINKS, sched=sched)
+    launches = {}
+    for env in ("", "0"):
+        monkeypatch.setenv("GS_SLICES", env)
+        sim, _ = compare(p, 5, LINKS, sched, batch=8, ref=ref)
+        st = sim.stats()
+        print(repr(env), {k: st[k] for k in ("batches", "gossip_fallback_batches", "gossip_list_batches",
+                                             "list_pull_batches", "relax_launches")})
+        assert st["batches"] == 4 and st["gossip_fallback_batches"] == 1 and st["gossip_list_batches"] == 4
+        launches[env] = st["relax_launches"]
+        sim.close()
+    assert launches[""] * 2 < launches["0"]
+
+
+def test_class_cuts_split_what_would_be_a_slice_group(monkeypatch):
+    """Publishes 1.5 heartbeats apart with batches of 8: the class regrouping
+    cuts every 8 messages into two lockstep batches of 4 (heartbeats 950 and
+    450 ms after the publishes), and a slice group must not reach across a cut.
+    On links of 10-50 ms every message is complete long before its first
+    heartbeat, so every no-op proof holds and a group that ignored the cuts
+    would succeed: the same schedule without the regrouping (GS_CLASS_SPLIT=0)
+    does run as one group of 4 mixed slices, 4 batches. With the cuts: 8
+    batches of 4, no full batch for a group. Both equal the oracle."""
+    monkeypatch.setenv("GS_SLICES", "")
+    monkeypatch.setenv("GS_REQUIRE_LPULL", "1")
+    N, M, links = 1200, 32, (50, 150, 10, 50)
+    p = oracle.params(peers=N, seed=370, hb_phase_ns=(T0 + 950_000_000) % HB)
+    t = T0 + np.arange(M, dtype=np.uint64) * np.uint64(1_500_000_000)
+    sched = (t, (6 + np.arange(M)) % N, np.full(M, 15000))
+    ref = oracle.simulate(p, 5, links, sched=sched)
+    for split, batches in (("", 8), ("0", 4)):
+        monkeypatch.setenv("GS_CLASS_SPLIT", split)
+        sim, _ = compare(p, 5, links, sched, batch=8, ref=ref)
+        st = sim.stats()
+        print(repr(split), {k: st[k] for k in ("batches", "messages", "gossip_noop_msgs", "gossip_fallback_batches",
+                                               "list_pull_batches", "relax_launches", "latency_max_ms")})
+        sim.close()
+        assert st["gossip_noop_msgs"] == M and st["gossip_fallback_batches"] == 0
+        assert st["batches"] == st["list_pull_batches"] == batches and st["messages"] == M
