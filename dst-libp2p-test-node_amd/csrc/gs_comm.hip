@@ -380,7 +380,8 @@ void rank_status(gs_comm* cm, Ctx& c, uint64_t mine) {
 // MAX of each word agree) before the first batch.
 void check_same_config(gs_comm* cm, Ctx& c, const gs_publish* sched, uint64_t n_msgs, uint64_t lat) {
   if (cm->local) return;
-  // FNV-1a over the schedule, and whether the sink takes the u16 latencies (lat_gate's collective)
+  // FNV-1a over the schedule, and whether the sink takes the u16 latencies (bit 0) or the delay
+  // accumulators do (bit 1: gs_set_peer_delay) — lat_gate's collective
   uint64_t h = (1469598103934665603ull ^ lat) * 1099511628211ull;
   for (uint64_t i = 0; i < n_msgs; i++) {
     const uint64_t v[4] = {sched[i].t_pub_ns, sched[i].publisher, sched[i].msg_size, sched[i].frags};
@@ -400,7 +401,7 @@ void check_same_config(gs_comm* cm, Ctx& c, const gs_publish* sched, uint64_t n_
   for (int k = 0; k < 8; k++)
     if (c.h_pinned[k] != c.h_pinned[8 + k])
       throw Error(GS_EINVAL, "RCCL ranks disagree on the partitioned run (peers, batch, lazy_gossip, idontwant, "
-                             "churn, fragments, seed, schedule or the latency stream)");
+                             "churn, fragments, seed, schedule, the latency stream or gs_set_peer_delay)");
 }
 
 // RCCL ranks: every rank's n words (n <= 4) -> out[rank * n + k] on the host.
@@ -419,7 +420,10 @@ void rank_gather(gs_comm* cm, Ctx& c, const uint64_t* mine, uint32_t n, uint64_t
 // and no rank failed the batch: the staged parts' error words (part_lat_stage), combined over
 // the ranks with the pass control's all-gather, before the first hand-over. Every rank then
 // fails the call alike, and none is left waiting in the next batch's collectives.
-bool wants_lat(const gs_result_sink* sinks, uint32_t i) { return sinks && sinks[i].on_lat; }
+// A part stages its latencies for its sink's on_lat (or the text), or for its delay accumulators.
+bool wants_lat(Ctx* const* cx, const gs_result_sink* sinks, uint32_t i) {
+  return cx[i]->pdelay || (sinks && sinks[i].on_lat);
+}
 
 void lat_gate(gs_comm* cm, Ctx** cx, uint32_t nctx) {
   uint64_t err = 0;
@@ -443,7 +447,7 @@ void lat_gate(gs_comm* cm, Ctx** cx, uint32_t nctx) {
 void lat_stage_all(gs_comm* cm, Ctx** cx, uint32_t nctx, const gs_result_sink* sinks, uint32_t B) {
   bool any = false;
   for (uint32_t i = 0; i < nctx; i++) {
-    if (!wants_lat(sinks, i)) continue;
+    if (!wants_lat(cx, sinks, i)) continue;
     GS_HIP(hipSetDevice(cx[i]->cfg.device));
     part_lat_stage(*cx[i], B, nullptr);
     any = true;
@@ -486,20 +490,24 @@ void run_batch_ms(gs_comm* cm, Ctx** cx, uint32_t nctx, const gs_publish* sched,
         ds.hops = c.d_ms_hops.p;
         const uint32_t batch = c.cfg.batch;
         const Ctx::TextRun text = c.text;
+        const bool pdelay = c.pdelay;
         c.cfg.batch = mpmax;  // buffers for this part's share, not the whole batch
         c.sink_dev = true;
         c.text = Ctx::TextRun{};  // (the log's text is of the own peers' rows, after the exchange)
+        c.pdelay = false;         // (and so are the delay accumulators' observations: part_lat_stage)
         try {
           run_messages(c, sched + i0 + m0, mp, &ds);
         } catch (...) {
           c.cfg.batch = batch;
           c.sink_dev = false;
           c.text = text;
+          c.pdelay = pdelay;
           throw;
         }
         c.cfg.batch = batch;
         c.sink_dev = false;
         c.text = text;
+        c.pdelay = pdelay;
       }
       c.stats.messages += B - mp;  // every part counts the batch, as in the peer protocols
       c.stats.batches = batches + 1;
@@ -574,21 +582,21 @@ void run_batch_ms(gs_comm* cm, Ctx** cx, uint32_t nctx, const gs_publish* sched,
   }
   // 3. own peers' rows into the sinks; the logged latencies of them from the exchanged
   // completion times (k_lat_rows), every part's before the gate and the first hand-over
-  if (!sinks) return;
   bool any = false;
   for (uint32_t i = 0; i < nctx; i++) {
-    if (!wants_lat(sinks, i)) continue;
+    if (!wants_lat(cx, sinks, i)) continue;
     GS_HIP(hipSetDevice(cx[i]->cfg.device));
     part_lat_stage(*cx[i], B, sched + i0);
     any = true;
   }
   if (any) lat_gate(cm, cx, nctx);
+  if (!sinks && !any) return;
   for (uint32_t i = 0; i < nctx; i++) {
     Ctx& c = *cx[i];
     const uint32_t me = cm->local ? i : cm->rank, un = lay.un(me);
     GS_HIP(hipSetDevice(c.cfg.device));
-    if (wants_lat(sinks, i)) part_lat_deliver_ms(c, B, &sinks[i], i0);
-    else deliver_rows(c, B, un, &sinks[i], i0);
+    if (wants_lat(cx, sinks, i)) part_lat_deliver_ms(c, B, sinks ? &sinks[i] : nullptr, i0);
+    else if (sinks) deliver_rows(c, B, un, &sinks[i], i0);
     GS_HIP(hipStreamSynchronize(c.stream));
   }
 }
@@ -1092,7 +1100,7 @@ void run_batch(gs_comm* cm, Ctx** cx, uint32_t nctx, const gs_publish* sched, ui
   bool ok = true;
   for (uint32_t i = 0; i < nctx; i++) {
     GS_HIP(hipSetDevice(cx[i]->cfg.device));
-    ok = part_dev_complete(*cx[i], sinks && sinks[i].summary, true, wants_lat(sinks, i)) && ok;
+    ok = part_dev_complete(*cx[i], sinks && sinks[i].summary, true, wants_lat(cx, sinks, i)) && ok;
   }
   if (!cm->local && cx[0]->cfg.lazy_gossip) {
     Ctx& c = *cx[0];
@@ -1138,12 +1146,14 @@ gs_status run_partitioned(gs_ctx* const* ctxs, uint32_t nctx, gs_comm* comm, con
       if (!cx[i]->mesh_built) cx[i]->fail(GS_ESTATE, "gs_mesh_converge first");
       if (cx[i]->cfg.peers != c0->cfg.peers || cx[i]->cfg.batch != c0->cfg.batch)
         c0->fail(GS_EINVAL, "every part needs the same peers and batch");
+      if (cx[i]->pdelay != c0->pdelay)
+        c0->fail(GS_EINVAL, "every part needs the same gs_set_peer_delay switch");
       GS_HIP(hipSetDevice(cx[i]->cfg.device));
       part_set(*cx[i], comm->nranks, comm->local ? i : comm->rank);
     }
     if (!comm->local && c0->cfg.device != comm->device)
       c0->fail(GS_EINVAL, "the context and the communicator must use the same device");
-    check_same_config(comm, *c0, sched, n_msgs, wants_lat(sinks, 0) ? 1 : 0);
+    check_same_config(comm, *c0, sched, n_msgs, ((sinks && sinks[0].on_lat) ? 1 : 0) | (c0->pdelay ? 2 : 0));
     uint64_t i0 = 0;
     while (i0 < n_msgs) {  // batches of equal size and chunk count, at most cfg.batch messages
       uint64_t i1 = i0 + 1;

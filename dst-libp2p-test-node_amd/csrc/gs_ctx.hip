@@ -253,6 +253,8 @@ extern "C" gs_status gs_run(gs_ctx* ctx, const gs_publish* sched, uint64_t n_msg
     ctx->fail(GS_EINVAL, "gs_result_sink.want: unknown bits");
   if (sink && (sink->on_lat != nullptr) != ((sink->want & GS_WANT_LAT_MS) != 0))
     ctx->fail(GS_EINVAL, "gs_result_sink: on_lat and GS_WANT_LAT_MS go together");
+  if (ctx->pdelay && ctx->part_parts > 1)  // (the accumulators cover the partition's rows, gs_run all peers)
+    ctx->fail(GS_EUNSUPPORTED, "gs_run with gs_set_peer_delay on a partitioned context: use gs_run_partitioned");
   GS_HIP(hipSetDevice(ctx->cfg.device));
   if (n_msgs) run_messages(*ctx, sched, n_msgs, sink);
   GS_API_END(ctx)
@@ -363,6 +365,41 @@ extern "C" gs_status gs_get_traffic(gs_ctx* ctx, uint64_t* traffic) {
   GS_API_END(ctx)
 }
 
+// ---- per-peer delay accumulators (gs_peerdelay.h) ----
+extern "C" gs_status gs_set_peer_delay(gs_ctx* ctx, uint32_t enable) {
+  GS_API_BEGIN(ctx)
+  if (ctx->part_open) ctx->fail(GS_ESTATE, "a partitioned batch is in flight (gs_part_finish first)");
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  peer_delay_set(*ctx, enable != 0);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_get_peer_delay(gs_ctx* ctx, gs_peer_delay* out) {
+  GS_API_BEGIN(ctx)
+  if (!out) ctx->fail(GS_EINVAL, "null delay array");
+  if (!ctx->pdelay) ctx->fail(GS_ESTATE, "gs_set_peer_delay(ctx, 1) first");
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  peer_delay_get(*ctx, out);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_reset_peer_delay(gs_ctx* ctx) {
+  GS_API_BEGIN(ctx)
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  peer_delay_reset(*ctx);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_peer_delay_add_lat(gs_ctx* ctx, const gs_publish* sched, uint64_t n_msgs,
+                                           const uint16_t* lat_ms) {
+  GS_API_BEGIN(ctx)
+  if ((!sched || !lat_ms) && n_msgs) ctx->fail(GS_EINVAL, "null schedule or latencies");
+  if (!ctx->pdelay) ctx->fail(GS_ESTATE, "gs_set_peer_delay(ctx, 1) first");
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  if (n_msgs) peer_delay_add_lat(*ctx, sched, n_msgs, lat_ms);
+  GS_API_END(ctx)
+}
+
 // ---- peer-partitioned mode (gs_part.h) ----
 extern "C" gs_status gs_set_partition(gs_ctx* ctx, uint32_t parts, uint32_t part) {
   GS_API_BEGIN(ctx)
@@ -375,6 +412,9 @@ extern "C" gs_status gs_part_begin(gs_ctx* ctx, const gs_publish* sched, uint64_
   GS_API_BEGIN(ctx)
   if (!ctx->mesh_built) ctx->fail(GS_ESTATE, "gs_mesh_converge first");
   if (!sched || !out_min_key) ctx->fail(GS_EINVAL, "null schedule or output");
+  if (ctx->pdelay)
+    ctx->fail(GS_EUNSUPPORTED, "per-peer delay accumulators (gs_set_peer_delay) are not supported by the caller-driven "
+                               "protocol: use gs_run_partitioned");
   GS_HIP(hipSetDevice(ctx->cfg.device));
   *out_min_key = part_begin(*ctx, sched, n_msgs);
   GS_API_END(ctx)

@@ -660,6 +660,74 @@ extern "C" gs_status gs_write_node_metrics(const gs_config* cfg, const char* pat
   return GS_OK;
 }
 
+// The nim node's application metrics (nim-test-node/gossipsub-queues/main.nim:25-78,
+// updated at main.nim:147-154) for every peer, in the Prometheus text exposition
+// format: "# HELP" (the node's help strings verbatim) and "# TYPE" per family, then
+// one series per peer labelled muxer and peer_id. The node's peer_id is its libp2p
+// PeerId; pod-<id> stands in for it (the host names of gs_write_node_metrics).
+// dst_testnode_received_chunks_total (main.nim:37-41) is not written: it counts
+// fragment first arrivals, which completion does not keep per peer.
+extern "C" gs_status gs_write_testnode_metrics(const gs_config* cfg, const char* path, const uint64_t* row_ptr,
+                                               const uint8_t* mesh_count, const gs_publish* sched, uint64_t n_msgs,
+                                               const gs_peer_delay* delay) {
+  if (!cfg || !path || !row_ptr || !mesh_count || !delay || (!sched && n_msgs)) return GS_EINVAL;
+  if (cfg->muxer > GS_MUX_MPLEX) return GS_EINVAL;
+  const uint32_t N = cfg->peers;
+  std::vector<uint64_t> published(N, 0);
+  for (uint64_t i = 0; i < n_msgs; i++) {
+    if (sched[i].publisher >= N) return GS_EINVAL;
+    published[sched[i].publisher]++;
+  }
+  FILE* f = fopen(path, "w");
+  if (!f) return GS_EINVAL;
+  std::vector<char> buf(1 << 20);
+  setvbuf(f, buf.data(), _IOFBF, buf.size());
+  static const char* const kMux[3] = {"yamux", "quic", "mplex"};
+  static const char* const kLe[GS_DELAY_BUCKETS] = {"1.0",   "5.0",   "10.0",   "25.0",   "50.0",   "100.0",
+                                                    "250.0", "500.0", "1000.0", "2500.0", "5000.0", "10000.0"};
+  const char* mux = kMux[cfg->muxer];
+  auto head = [&](const char* name, const char* type, const char* help) {
+    fprintf(f, "# HELP %s %s\n# TYPE %s %s\n", name, help, name, type);
+  };
+  auto family = [&](const char* name, const char* type, const char* help, auto value) {
+    head(name, type, help);
+    for (uint32_t u = 0; u < N; u++)
+      fprintf(f, "%s{muxer=\"%s\",peer_id=\"pod-%u\"} %llu\n", name, mux, u, (unsigned long long)value(u));
+  };
+  family("dst_testnode_publish_requests_total", "counter", "number of /publish requests accepted by the test node",
+         [&](uint32_t u) { return published[u]; });
+  family("dst_testnode_publish_failures_total", "counter", "number of failed local publish attempts",
+         [](uint32_t) { return 0ull; });
+  family("dst_testnode_completed_messages_total", "counter", "number of application-level messages fully received",
+         [&](uint32_t u) { return delay[u].completed; });
+  family("dst_testnode_message_delay_ms_sum", "counter", "sum of message delays in milliseconds (use with rate)",
+         [&](uint32_t u) { return delay[u].delay_sum_ms; });
+  head("dst_testnode_message_delay_ms", "histogram", "message delay histogram for percentile analysis");
+  for (uint32_t u = 0; u < N; u++) {
+    uint64_t cum = 0;
+    for (uint32_t i = 0; i < GS_DELAY_BUCKETS; i++) {
+      cum += delay[u].bucket[i];
+      fprintf(f, "dst_testnode_message_delay_ms_bucket{muxer=\"%s\",peer_id=\"pod-%u\",le=\"%s\"} %llu\n", mux, u,
+              kLe[i], (unsigned long long)cum);
+    }
+    cum += delay[u].bucket[GS_DELAY_BUCKETS];
+    fprintf(f, "dst_testnode_message_delay_ms_bucket{muxer=\"%s\",peer_id=\"pod-%u\",le=\"+Inf\"} %llu\n", mux, u,
+            (unsigned long long)cum);
+    fprintf(f, "dst_testnode_message_delay_ms_sum{muxer=\"%s\",peer_id=\"pod-%u\"} %llu\n", mux, u,
+            (unsigned long long)delay[u].delay_sum_ms);
+    fprintf(f, "dst_testnode_message_delay_ms_count{muxer=\"%s\",peer_id=\"pod-%u\"} %llu\n", mux, u,
+            (unsigned long long)cum);
+  }
+  family("dst_testnode_last_message_delay_ms", "gauge", "last observed message delay in milliseconds (real-time)",
+         [&](uint32_t u) { return (uint64_t)delay[u].last_ms; });
+  family("dst_testnode_mesh_size", "gauge", "current GossipSub mesh size for the test topic",
+         [&](uint32_t u) { return (uint64_t)mesh_count[u]; });
+  family("dst_testnode_topic_peers", "gauge", "current number of GossipSub peers for the test topic",
+         [&](uint32_t u) { return row_ptr[u + 1] - row_ptr[u]; });
+  if (fclose(f)) return GS_EINVAL;
+  return GS_OK;
+}
+
 // shadow/run.sh:34-36 + shadow/README.md:76-78: publisher_id, rotation 0/1,
 // inter_message_delay. tx_time is the publish instant (main.rs:105-111).
 extern "C" gs_status gs_schedule_runsh(uint32_t n_msgs, uint32_t peers, uint32_t publisher_id,

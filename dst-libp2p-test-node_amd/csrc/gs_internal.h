@@ -105,6 +105,10 @@ struct Ctx {
   bool timing = false;
   bool traffic = false;        // gs_set_traffic: per-peer send/receive counters
   DevBuf<uint64_t> d_traffic;  // [N][GS_TRAFFIC_COLS]
+  // gs_set_peer_delay (gs_peerdelay.h): per-peer delay accumulators of the context's own rows
+  bool pdelay = false;
+  DevBuf<uint64_t> d_pdelay;   // [PD_COLS][own rows]
+  uint32_t pdelay_n = 0;       // the rows d_pdelay covers (0: zeroed at the next use, part_set after a new split)
 
   // links
   uint32_t S = 0;
@@ -390,6 +394,11 @@ void deliver_rows(Ctx& c, uint32_t B, uint32_t un, const gs_result_sink* sink, u
 // the arrival log as text (gs_logtext.h): c.text holds the callback
 void format_lat_log(Ctx& c, const gs_publish* sched, uint64_t n_msgs, const uint16_t* lat_ms);
 void log_text_reset(Ctx& c);
+// per-peer delay accumulators (gs_peerdelay.h)
+void peer_delay_set(Ctx& c, bool on);
+void peer_delay_reset(Ctx& c);
+void peer_delay_get(Ctx& c, gs_peer_delay* out);
+void peer_delay_add_lat(Ctx& c, const gs_publish* sched, uint64_t n_msgs, const uint16_t* lat_ms);
 void part_set(Ctx& c, uint32_t parts, uint32_t part);
 uint64_t part_begin(Ctx& c, const gs_publish* sched, uint64_t n_msgs);
 bool part_scan(Ctx& c, uint64_t bucket_key, gs_part_record* rec, uint64_t cap, uint64_t* n, uint64_t* m1);

@@ -332,6 +332,7 @@ static void deliver_text(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, uint6
   dim3 tg((un + 63) / 64, (b.B + 63) / 64);
   k_transpose16<<<tg, TB, 0, s>>>(c.d_lat.p, c.d_lat_t.p, un, b.B);
   GS_HIP(hipGetLastError());
+  pd_accumulate(c, c.d_lat_t.p, c.d_tpub.p, b.B, un);  // (a staged batch: part_lat_stage did)
   GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_counters.p + C_ERR, 8, hipMemcpyDeviceToHost, s));
   GS_HIP(hipStreamSynchronize(s));
   if (c.h_pinned[0] & ERR_LAT16)  // before any text of the batch is handed out

@@ -364,7 +364,8 @@ void part_set(Ctx& c, uint32_t parts, uint32_t part) {
   const uint32_t N = c.cfg.peers;
   if (c.part_open) c.fail(GS_ESTATE, "a partitioned batch is in flight (gs_part_finish first)");
   if (parts < 1 || part >= parts || parts > N) c.fail(GS_EINVAL, "need 1 <= parts <= peers and part < parts");
-  if (parts != c.part_parts || part != c.part_idx) c.tcnt_n = 0;  // the log text's line counters start over
+  if (parts != c.part_parts || part != c.part_idx)
+    c.tcnt_n = c.pdelay_n = 0;  // the log text's line counters and the delay accumulators start over
   c.part_parts = parts;
   c.part_idx = part;
   const PartLayout lay{parts, N, 0};
@@ -653,7 +654,8 @@ void part_abort(Ctx& c) {
 // every part's error word before any part hands out a line or a block of the batch.
 // part_lat_stage, enqueued: d_lat_t[B][un] message-major — transposed from the completion's
 // peer-major d_lat, or for a message-sharded batch (ms_sched: its B schedule rows) from the
-// exchanged d_tc_t by k_lat_rows — then, when the latencies leave as text, the line counters'
+// exchanged d_tc_t by k_lat_rows — then the delay accumulators' share of the batch
+// (gs_set_peer_delay: the own rows, once) and, when the latencies leave as text, the line counters'
 // room for the batch (k_lt_room), and the error word on its way into h_pinned[30].
 void part_lat_stage(Ctx& c, uint32_t B, const gs_publish* ms_sched) {
   hipStream_t s = c.stream;
@@ -674,11 +676,13 @@ void part_lat_stage(Ctx& c, uint32_t B, const gs_publish* ms_sched) {
     k_lat_rows<<<dim3((un + TB - 1) / TB, B), TB, 0, s>>>(c.d_tc_t.p, c.d_lr_tpub.p, c.d_lr_pub.p, c.d_lat_t.p, un,
                                                           c.part_u0, c.cfg.self_log, c.d_counters.p);
     GS_HIP(hipGetLastError());
+    pd_accumulate(c, c.d_lat_t.p, c.d_lr_tpub.p, B, un);
     GS_HIP(hipStreamSynchronize(s));  // (tp / pb leave scope)
   } else {
     dim3 tg((un + 63) / 64, (B + 63) / 64);
     k_transpose16<<<tg, TB, 0, s>>>(c.d_lat.p, c.d_lat_t.p, un, B);
     GS_HIP(hipGetLastError());
+    pd_accumulate(c, c.d_lat_t.p, c.d_tpub.p, B, un);
   }
   if (c.text.fn) {
     lt_counters(c, un);
@@ -695,11 +699,12 @@ uint64_t part_lat_err(Ctx& c) {
   return c.h_pinned[30] & (ERR_LAT16 | ERR_LINES);
 }
 
-// A staged message-sharded batch into the sink: its text, or the rows / on_lat blocks.
+// A staged message-sharded batch into the sink: its text, or the rows / on_lat blocks
+// (no sink: it was staged for the delay accumulators alone).
 void part_lat_deliver_ms(Ctx& c, uint32_t B, const gs_result_sink* sink, uint64_t row0) {
   c.lat_staged = false;
   if (c.text.fn) text_emit(c, c.d_lat_t.p, B, c.text.sched + row0, row0, c.part_u0, c.part_un);
-  else deliver_rows(c, B, c.part_un, sink, row0);
+  else if (sink) deliver_rows(c, B, c.part_un, sink, row0);
 }
 
 void part_finish(Ctx& c, const gs_result_sink* sink) {
@@ -1010,7 +1015,7 @@ void part_lp_route_fix(Ctx& c, uint32_t P, uint32_t me, const uint64_t* base) {
 // unless the sink takes rows or a summary, or the rows hold fragment groups
 // (k_lfinal -> dense rows -> k_complete).
 void part_lp_end_enqueue(Ctx& c, const gs_result_sink* sink) {
-  const SinkWants w = sink_wants(sink);
+  const SinkWants w = sink_wants(c, sink);
   const bool dense = w.rows() || w.summary || c.part_b.FP > 1 || getenv("GS_LPULL_DENSE");
   if (dense) {
     const LPullArgs la = part_lp_args(c);

@@ -660,15 +660,21 @@ static void fill_summary(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, gs_ms
   }
 }
 
+#include "gs_peerdelay.h"
+
 // What a sink takes from a batch (include/gossipsim.h gs_result_sink): with
 // on_block the want bits select t_complete / hops (neither = both), without
 // it the non-NULL arrays do; on_lat takes the logged latency (GS_WANT_LAT_MS).
+// lat: the batch's logged latencies are needed — by the sink's on_lat, or by the
+// context's delay accumulators (gs_set_peer_delay; the one place that switch
+// becomes a want: the completion then writes d_lat and no batch runs without its log).
 struct SinkWants {
-  bool tc = false, h = false, lat = false, summary = false;
+  bool tc = false, h = false, lat = false, on_lat = false, summary = false;
   bool rows() const { return tc || h; }
 };
-static SinkWants sink_wants(const gs_result_sink* sink) {
+static SinkWants sink_wants(const Ctx& c, const gs_result_sink* sink) {
   SinkWants w;
+  w.lat = c.pdelay;
   if (!sink) return w;
   if (sink->on_block) {
     uint32_t th = sink->want & (GS_WANT_T_COMPLETE | GS_WANT_HOPS);
@@ -679,7 +685,8 @@ static SinkWants sink_wants(const gs_result_sink* sink) {
     w.tc = sink->t_complete_ns != nullptr;
     w.h = sink->hops != nullptr;
   }
-  w.lat = sink->on_lat != nullptr;
+  w.on_lat = sink->on_lat != nullptr;
+  w.lat = w.lat || w.on_lat;
   w.summary = sink->summary != nullptr;
   return w;
 }
@@ -692,13 +699,13 @@ static SinkWants sink_wants(const gs_result_sink* sink) {
 // runs while the caller's callbacks consume block k - 1).
 void deliver_rows(Ctx& c, uint32_t B, uint32_t un, const gs_result_sink* sink, uint64_t sink_row0) {
   hipStream_t s = c.stream;
-  const SinkWants w = sink_wants(sink);
+  const SinkWants w = sink_wants(c, sink);
   if (!sink->on_block && w.rows()) {
     const hipMemcpyKind kind = c.sink_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (w.tc) GS_HIP(hipMemcpyAsync(sink->t_complete_ns + sink_row0 * un, c.d_tc_t.p, (size_t)B * un * 8, kind, s));
     if (w.h) GS_HIP(hipMemcpyAsync(sink->hops + sink_row0 * un, c.d_hops_t.p, (size_t)B * un, kind, s));
   }
-  const bool st_rows = sink->on_block != nullptr, st_lat = w.lat;
+  const bool st_rows = sink->on_block != nullptr, st_lat = w.on_lat;
   if (!st_rows && !st_lat) return;
   const uint32_t bm = std::max<uint32_t>(1, std::min<uint32_t>(sink->block_msgs ? sink->block_msgs : 64, B));
   const size_t cell = (st_rows && w.tc ? 8 : 0) + (st_lat ? 2 : 0) + (st_rows && w.h ? 1 : 0);
@@ -776,6 +783,7 @@ static void deliver_lat_async(Ctx& c, const Batch& b, uint32_t un, const gs_resu
   dim3 tg((un + 63) / 64, (b.B + 63) / 64);
   k_transpose16<<<tg, TB, 0, s>>>(c.d_lat.p, lt.p, un, b.B);
   GS_HIP(hipGetLastError());
+  pd_accumulate(c, lt.p, c.d_tpub.p, b.B, un);
   const size_t bytes = (size_t)b.B * un * 2;
   if (c.h_lat_bytes[par] < bytes) {
     if (c.h_lat[par]) GS_HIP(hipHostFree(c.h_lat[par]));
@@ -813,16 +821,16 @@ static void deliver_lat_async(Ctx& c, const Batch& b, uint32_t un, const gs_resu
 // summaries.
 static void deliver(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, const gs_result_sink* sink,
                     uint64_t sink_row0) {
-  if (!sink) return;
+  const SinkWants w = sink_wants(c, sink);
+  if (!sink && !w.lat) return;  // (no sink: the delay accumulators still take the batch)
   hipStream_t s = c.stream;
-  const SinkWants w = sink_wants(sink);
   if (c.keys_none && (w.rows() || w.lat || w.summary))
     c.fail(GS_EINVAL, "internal: a sink's results after a no-log list pass");
   if (c.text.fn) {  // gs_run_log: the latencies leave as text (its sink asks for nothing else)
     deliver_text(c, b, u0, un, sink_row0);
     return;
   }
-  if (c.lat_async && w.lat && !w.rows() && !w.summary && sink->on_lat) {
+  if (c.lat_async && w.on_lat && !w.rows() && !w.summary) {
     deliver_lat_async(c, b, un, sink, sink_row0);
     return;
   }
@@ -841,12 +849,13 @@ static void deliver(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, const gs_r
     dim3 tg((un + 63) / 64, (b.B + 63) / 64);
     k_transpose16<<<tg, TB, 0, s>>>(c.d_lat.p, c.d_lat_t.p, un, b.B);
     GS_HIP(hipGetLastError());
+    pd_accumulate(c, c.d_lat_t.p, c.d_tpub.p, b.B, un);
     GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_counters.p + C_ERR, 8, hipMemcpyDeviceToHost, s));
     GS_HIP(hipStreamSynchronize(s));
     if (c.h_pinned[0] & ERR_LAT16) c.fail(GS_ERANGE, "a logged latency of 65535 ms or more does not fit the u16 "
-                                                     "stream (GS_WANT_LAT_MS)");
+                                                     "stream (GS_WANT_LAT_MS, gs_set_peer_delay)");
   }
-  if (w.rows() || w.lat) deliver_rows(c, b.B, un, sink, sink_row0);
+  if (w.rows() || w.on_lat) deliver_rows(c, b.B, un, sink, sink_row0);
   if (w.summary) fill_summary(c, b, u0, un, sink->summary + sink_row0);
 }
 
@@ -854,7 +863,7 @@ static void deliver(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, const gs_r
 static void launch_complete(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, const gs_result_sink* sink,
                             uint64_t sink_row0, size_t r0 = 0) {
   const bool hist = sink && sink->summary;
-  const SinkWants w = sink_wants(sink);
+  const SinkWants w = sink_wants(c, sink);
   run_complete(c, b, u0, un, hist, hist, w.rows() || w.summary, w.lat, r0);  // k_pct reads d_tc
   deliver(c, b, u0, un, sink, sink_row0);
 }

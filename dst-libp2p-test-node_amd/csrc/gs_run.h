@@ -544,7 +544,7 @@ struct Run {
 
   Run(Ctx& cc, const gs_publish* sched_, uint64_t n, const gs_result_sink* sink_, const std::vector<uint8_t>* cut_)
       : c(cc), sched(sched_), n_msgs(n), sink(sink_), cut(cut_), N(cc.cfg.peers), Bmax(cc.cfg.batch),
-        sw(sink_wants(sink_)), async_off(cc), pipe_on(chain_pipe_wanted(cc)), pass_stream(cc, pipe_on),
+        sw(sink_wants(cc, sink_)), async_off(cc), pipe_on(chain_pipe_wanted(cc)), pass_stream(cc, pipe_on),
         gossip(cc.cfg.lazy_gossip != 0), churn(cc.cfg.churn_ppm != 0), q0v(Bmax), r0v(Bmax), rel0(Bmax),
         habs0(Bmax), q0a(Bmax), r0a(Bmax), malive(Bmax), ah(cc) {
     hipStream_t s = c.stream;

@@ -97,6 +97,19 @@ class GsCommOps(ctypes.Structure):  # gs_comm_ops (ABI 10)
     _fields_ = [("user", ctypes.c_void_p), ("allgather", ALLGATHER_FN), ("exchange", EXCHANGE_FN)]
 
 
+DELAY_BOUNDS_MS = (1, 5, 10, 25, 50, 100, 250, 500, 1000, 2500, 5000, 10000)  # main.nim:59; GS_DELAY_BUCKETS
+
+
+class GsPeerDelay(ctypes.Structure):  # gs_peer_delay
+    _fields_ = [("completed", u64), ("delay_sum_ms", u64), ("last_rx_ns", u64), ("last_ms", u32), ("reserved", u32),
+                ("bucket", u64 * (len(DELAY_BOUNDS_MS) + 1))]
+
+
+# the same layout as a numpy structured dtype (Simulator.peer_delay)
+PEER_DELAY_DTYPE = np.dtype([("completed", "<u8"), ("delay_sum_ms", "<u8"), ("last_rx_ns", "<u8"), ("last_ms", "<u4"),
+                             ("reserved", "<u4"), ("bucket", "<u8", (len(DELAY_BOUNDS_MS) + 1,))])
+
+
 class GsPartRecord(ctypes.Structure):
     _fields_ = [("key", u64), ("start", u64), ("peer", u32), ("slot", u32)]
 
@@ -120,6 +133,12 @@ SIGNATURES = {
     "gs_write_node_metrics": (i32, [P(GsConfig), ctypes.c_char_p, P(u64), P(u8), P(u64)]),
     "gs_set_traffic": (i32, [ctypes.c_void_p, u32]),
     "gs_get_traffic": (i32, [ctypes.c_void_p, P(u64)]),
+    "gs_set_peer_delay": (i32, [ctypes.c_void_p, u32]),
+    "gs_get_peer_delay": (i32, [ctypes.c_void_p, P(GsPeerDelay)]),
+    "gs_reset_peer_delay": (i32, [ctypes.c_void_p]),
+    "gs_peer_delay_add_lat": (i32, [ctypes.c_void_p, P(GsPublish), u64, P(ctypes.c_uint16)]),
+    "gs_write_testnode_metrics": (i32, [P(GsConfig), ctypes.c_char_p, P(u64), P(u8), P(GsPublish), u64,
+                                        P(GsPeerDelay)]),
     "gs_topogen_links": (i32, [u32, u32, u32, u32, u32, u32, P(u64), P(u64)]),
     "gs_schedule_runsh": (i32, [u32, u32, u32, u32, u64, u64, u32, P(GsPublish)]),
     "gs_shadow_injector": (i32, [ctypes.c_char_p, P(GsInjector)]),
@@ -248,6 +267,22 @@ def write_node_metrics(cfg, path, row_ptr, mesh_count, traffic):
     rc = lib().gs_write_node_metrics(ctypes.byref(cfg.c), path.encode(), _ptr(row, u64), _ptr(mc, u8), _ptr(tr, u64))
     if rc:
         raise GossipSimError(rc, "gs_write_node_metrics failed")
+
+
+def write_testnode_metrics(cfg, path, row_ptr, mesh_count, schedule, delay):
+    """Prometheus text of the nim node's application metrics (dst_testnode_*, nim gossipsub-queues
+    main.nim:25-78) for every peer (gs_write_testnode_metrics). schedule: a GsPublish array
+    (publish requests per peer); delay: a PEER_DELAY_DTYPE array [peers] (Simulator.peer_delay,
+    the parts' arrays concatenated)."""
+    row = np.ascontiguousarray(row_ptr, np.uint64)
+    mc = np.ascontiguousarray(mesh_count, np.uint8)
+    pd = np.ascontiguousarray(delay, PEER_DELAY_DTYPE)
+    if pd.shape != (cfg.peers,) or row.shape != (cfg.peers + 1,) or mc.shape != (cfg.peers,):
+        raise GossipSimError(GS_EINVAL, "row_ptr [peers + 1], mesh_count [peers] and delay [peers] are needed")
+    rc = lib().gs_write_testnode_metrics(ctypes.byref(cfg.c), path.encode(), _ptr(row, u64), _ptr(mc, u8), schedule,
+                                         len(schedule), _ptr(pd, GsPeerDelay))
+    if rc:
+        raise GossipSimError(rc, "gs_write_testnode_metrics failed")
 
 
 def links_from_gml(path, shortest=False):
@@ -656,6 +691,40 @@ class Simulator:
     def write_node_metrics(self, path):
         """Every peer's Prometheus metrics (rust-test-node/src/metrics.rs names) after traffic runs."""
         write_node_metrics(self.cfg, path, self.csr()[0], self.mesh()[1], self.traffic())
+
+    # ---- what each node shows about delay (gs_set_peer_delay, DESIGN.md §2.13) ----
+    def _own_rows(self):
+        u0, u1 = getattr(self, "part_range", (0, self.peers))
+        return u1 - u0
+
+    def set_peer_delay(self, on=True):
+        """Per-peer delay accumulators (completed, delay sum, histogram, last delay) of later
+        runs, kept on the device whatever the runs' sinks take (zeroed now)."""
+        self._check(lib().gs_set_peer_delay(self.ctx, 1 if on else 0))
+
+    def peer_delay(self):
+        """-> PEER_DELAY_DTYPE array [own peers]: completed, delay_sum_ms, last_rx_ns, last_ms,
+        bucket[13] (not cumulative; bounds DELAY_BOUNDS_MS, the last one above 10000 ms)."""
+        out = np.zeros(self._own_rows(), PEER_DELAY_DTYPE)
+        self._check(lib().gs_get_peer_delay(self.ctx, _ptr(out, GsPeerDelay)))
+        return out
+
+    def reset_peer_delay(self):
+        self._check(lib().gs_reset_peer_delay(self.ctx))
+
+    def peer_delay_add_lat(self, schedule, lat_ms):
+        """Add a stored latency stream lat_ms[M, own peers] uint16 (LAT_NONE = no observation)
+        to the accumulators; needs no topology."""
+        schedule = self._schedule(schedule)
+        lat = np.ascontiguousarray(lat_ms, np.uint16)
+        if lat.shape != (len(schedule), self._own_rows()):
+            raise GossipSimError(GS_EINVAL, "lat_ms must be [len(schedule), own peers]")
+        self._check(lib().gs_peer_delay_add_lat(self.ctx, schedule, len(schedule), _ptr(lat, ctypes.c_uint16)))
+
+    def write_testnode_metrics(self, path, schedule):
+        """Every peer's nim-node metrics (dst_testnode_*) after runs of `schedule` with set_peer_delay."""
+        write_testnode_metrics(self.cfg, path, self.csr()[0], self.mesh()[1], self._schedule(schedule),
+                               self.peer_delay())
 
     def open_log(self, path):
         """Streaming arrival log (gs_log_open); feed it with LogStream.write(schedule_rows, t_complete)."""

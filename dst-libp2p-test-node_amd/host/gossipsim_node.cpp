@@ -26,8 +26,11 @@ void usage() {
           "         [--delay-ms MS] [--t0-s SECONDS] [--http-us US] [--max-heartbeats H] [--latencies PATH]\n"
           "         [--device-log]\n"
           "         [--gml network_topology.gml --yaml shadow.yaml] [--schedule FILE] [--shadowlog PATH] [--metrics PATH]\n"
+          "         [--testnode-metrics PATH]\n"
           "  --yaml also supplies the injector's -s/-m/-d and start_time unless given on the command line\n"
           "  --device-log writes --latencies from the device-formatted text (gs_run_log), one fwrite per chunk\n"
+          "  --testnode-metrics writes the nim node's per-peer delay metrics (dst_testnode_*, gs_set_peer_delay);\n"
+          "    a run with a latency of 65535 ms or more then fails\n"
           "env: PEERS CONNECTTO FRAGMENTS MUXER MAXCONNECTIONS GOSSIPSUB_* SELFTRIGGER GS_NODE GS_SEED GS_BATCH\n"
           "     GS_DEVICE\n");
 }
@@ -114,7 +117,7 @@ int main(int argc, char** argv) {
   // the POST reaches the node 1.5 round trips over the 1 ms injector-hub links
   // after the injector sends it (topogen.py:64-69); tx_time is stamped then
   uint64_t http_us = 3000;
-  std::string latencies, gml, yaml, shadowlog, metrics, schedule;
+  std::string latencies, gml, yaml, shadowlog, metrics, schedule, testnode;
   bool set_size = false, set_msgs = false, set_delay = false, set_t0 = false, device_log = false;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -142,6 +145,7 @@ int main(int argc, char** argv) {
     else if (a == "--yaml") yaml = next();          // ... and its host placement (topogen.py output)
     else if (a == "--shadowlog") shadowlog = next(); // tracker counters for summary_shadowlog.awk
     else if (a == "--metrics") metrics = next();    // the node metrics (rust-test-node/src/metrics.rs)
+    else if (a == "--testnode-metrics") testnode = next();  // the nim node's metrics (gossipsub-queues/main.nim:25-78)
     else if (a == "--schedule") schedule = next();  // rows: t_pub_ns publisher msg_size [frags]
     else { usage(); return 2; }
   }
@@ -183,6 +187,7 @@ int main(int argc, char** argv) {
     return die(ctx, st, "gs_set_links");
   const bool counters = !shadowlog.empty() || !metrics.empty();
   if (counters && (st = gs_set_traffic(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_traffic");
+  if (!testnode.empty() && (st = gs_set_peer_delay(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_peer_delay");
   if ((st = gs_build_topology(ctx)) != GS_OK) return die(ctx, st, "gs_build_topology");
   uint32_t epochs = 0;
   if ((st = gs_mesh_converge(ctx, max_hb, &epochs)) != GS_OK) return die(ctx, st, "gs_mesh_converge");
@@ -219,7 +224,7 @@ int main(int argc, char** argv) {
     if (fclose(out.f) || !out.ok) return die(ctx, GS_EINVAL, "fwrite --latencies");
     if (st == GS_OK) {
       text_done = true;
-    } else if (st == GS_ERANGE) {  // as below: the run again through the completion times
+    } else if (st == GS_ERANGE && testnode.empty()) {  // as below: the run again through the completion times
       wide_only = true;
       gs_log_text_reset(ctx);
     } else {
@@ -234,7 +239,8 @@ int main(int argc, char** argv) {
   sink.user = &strm;
   sink.block_msgs = 16;
   if (!text_done && !wide_only) st = gs_run(ctx, sched.data(), n_msgs, &sink);
-  if (wide_only || (st == GS_ERANGE && strstr(gs_last_error(ctx), "GS_WANT_LAT_MS"))) {
+  // (with --testnode-metrics the delay accumulators take the u16 latencies too: the error stands)
+  if (wide_only || (st == GS_ERANGE && testnode.empty() && strstr(gs_last_error(ctx), "GS_WANT_LAT_MS"))) {
     // a latency the u16 stream cannot carry: the same run again (it is
     // deterministic) through the u64 completion times, the log from the start
     if (strm.log) gs_log_close(strm.log);
@@ -286,6 +292,17 @@ int main(int argc, char** argv) {
       return die(ctx, st, "gs_write_shadow_heartbeat");
     if (!metrics.empty() && (st = gs_write_node_metrics(&cfg, metrics.c_str(), row.data(), mc.data(), tr.data())) != GS_OK)
       return die(ctx, st, "gs_write_node_metrics");
+  }
+  if (!testnode.empty()) {
+    std::vector<gs_peer_delay> pd(cfg.peers);
+    std::vector<uint64_t> row((size_t)cfg.peers + 1);
+    std::vector<uint8_t> mc(cfg.peers);
+    if ((st = gs_get_peer_delay(ctx, pd.data())) != GS_OK) return die(ctx, st, "gs_get_peer_delay");
+    if ((st = gs_get_csr(ctx, row.data(), nullptr, nullptr)) != GS_OK) return die(ctx, st, "gs_get_csr");
+    if ((st = gs_get_mesh(ctx, nullptr, mc.data())) != GS_OK) return die(ctx, st, "gs_get_mesh");
+    if ((st = gs_write_testnode_metrics(&cfg, testnode.c_str(), row.data(), mc.data(), sched.data(), n_msgs,
+                                        pd.data())) != GS_OK)
+      return die(ctx, st, "gs_write_testnode_metrics");
   }
   gs_destroy(ctx);
   return 0;

@@ -478,6 +478,72 @@ gs_status gs_set_traffic(struct gs_ctx* ctx, uint32_t enable);
 /* Copy the per-peer counters out: traffic[peers][GS_TRAFFIC_COLS]. */
 gs_status gs_get_traffic(struct gs_ctx* ctx, uint64_t* traffic);
 
+/* ---- what each node shows about delay ---------------------
+ * The per-peer application metrics of nim-test-node/gossipsub-queues
+ * (main.nim:25-78,147-154), reduced on the device from the logged latencies
+ * every completion path produces. An observation is exactly an arrival-log
+ * line: a (peer, message) pair that is delivered, the publisher's own row only
+ * with cfg.self_log (then at delay 0). The delay is the logged ms
+ * ((t_complete - tx_time) / 1e6 truncated). */
+#define GS_DELAY_BUCKETS 12u   /* le = 1,5,10,25,50,100,250,500,1000,2500,5000,10000 ms (main.nim:59) */
+typedef struct gs_peer_delay {
+    uint64_t completed;      /* observations = log lines of this peer (main.nim:151)              */
+    uint64_t delay_sum_ms;   /* main.nim:152                                                      */
+    uint64_t last_rx_ns;     /* t_pub_ns + last_ms * 1e6 of the last observation; 0 if none       */
+    uint32_t last_ms;        /* main.nim:154                                                      */
+    uint32_t reserved;       /* 0                                                                 */
+    uint64_t bucket[GS_DELAY_BUCKETS + 1]; /* NOT cumulative: bucket[i] counts bound[i-1] < ms <= bound[i], */
+                                           /* bucket[0] ms <= 1 (0 included), bucket[12] ms > 10000         */
+} gs_peer_delay;
+
+/* 1: every batch of gs_run, gs_run_log, gs_run_partitioned and
+ * gs_run_partitioned_log adds its observations to per-peer accumulators on the
+ * device, whatever the sink asks for and with a NULL sink (the completion then
+ * writes the logged latencies, so no batch runs without its log). Off by
+ * default; enabling allocates and zeroes the accumulators. They cover the
+ * context's own rows — all peers, or the range of its partition — carry across
+ * batches and calls, and are zeroed by gs_reset_peer_delay, by enabling, and
+ * when the context's partition (parts, part) changes. After a failed run call
+ * they are unspecified until gs_reset_peer_delay.
+ * "Last" is the observation that maximises (t_pub_ns + ms * 1e6, t_pub_ns): it
+ * depends on no processing order, and orders completions at ms grain (the node
+ * orders them by wall clock: two completions at one peer less than 1 ms apart
+ * may swap).
+ * While the switch is on, a logged latency of 65535 ms or more fails the run
+ * call with GS_ERANGE, as for every consumer of the u16 latencies.
+ * Partitioned mode: gs_part_begin (the caller-driven protocol) returns
+ * GS_EUNSUPPORTED while the switch is on, and so does gs_run on a context that
+ * holds one of several parts (as gs_run_log); all contexts (and ranks) of a
+ * gs_run_partitioned* call must agree on it (GS_EINVAL).
+ * gs_save_state does not carry the accumulators: a loaded context has the
+ * switch off. */
+gs_status gs_set_peer_delay(struct gs_ctx*, uint32_t enable);
+/* out[own rows]. GS_ESTATE while the switch is off. */
+gs_status gs_get_peer_delay(struct gs_ctx*, gs_peer_delay* out);
+gs_status gs_reset_peer_delay(struct gs_ctx*);
+/* Add a caller's archived on_lat stream lat_ms[n_msgs][own rows] (GS_LAT_NONE
+ * where no line is logged): needs only gs_create and the switch, no graph. The
+ * stream is uploaded in pieces of at most cfg.batch messages. */
+gs_status gs_peer_delay_add_lat(struct gs_ctx*, const gs_publish* sched, uint64_t n_msgs, const uint16_t* lat_ms);
+
+/* The nim node's Prometheus metrics (nim-test-node/gossipsub-queues
+ * main.nim:25-78, help strings verbatim) for every peer, in the text exposition
+ * format ("# HELP" / "# TYPE" per family), one series per peer labelled
+ * muxer="yamux|quic|mplex", peer_id="pod-<id>" (the node prints its libp2p
+ * PeerId, which cannot be derived; pod-<id> matches gs_write_node_metrics):
+ * dst_testnode_publish_requests_total (counted from sched),
+ * dst_testnode_publish_failures_total (0), dst_testnode_completed_messages_total,
+ * dst_testnode_message_delay_ms_sum, the histogram dst_testnode_message_delay_ms
+ * (cumulative _bucket{le=...}, _sum, _count), dst_testnode_last_message_delay_ms,
+ * dst_testnode_mesh_size (mesh_count) and dst_testnode_topic_peers (CSR degree).
+ * dst_testnode_received_chunks_total is not written: it counts fragment first
+ * arrivals, which completion does not keep per peer. Arrays are host copies:
+ * row_ptr[peers+1], mesh_count[peers], delay[peers] (gs_get_peer_delay; the
+ * parts' arrays side by side). Host only. */
+gs_status gs_write_testnode_metrics(const gs_config* cfg, const char* path, const uint64_t* row_ptr,
+                                    const uint8_t* mesh_count, const gs_publish* sched, uint64_t n_msgs,
+                                    const gs_peer_delay* delay);
+
 /* ---- peer-partitioned mode -------------------------
  * Context `part` of `parts` owns the keys of peers [part*N/parts,
  * (part+1)*N/parts); topology and mesh are built identically (replicated) in

@@ -18,6 +18,7 @@ pub const GS_NODE_RUST: u32 = 0;
 pub const GS_TRAFFIC_COLS: usize = 12; // GS_TR_*: tx/rx bytes, packets, header bytes, received,
                                        // published, tx/rx ACK packets, tx/rx ACK header bytes
 pub const GS_HIST_BINS: usize = 64;
+pub const GS_DELAY_BUCKETS: usize = 12; // le = 1 .. 10000 ms (nim gossipsub-queues main.nim:59)
 pub const GS_CTRL_IHAVE: u32 = 0;
 pub const GS_CTRL_IWANT: u32 = 1;
 pub const GS_CTRL_ACK: u32 = 2;
@@ -39,6 +40,11 @@ pub struct gs_publish { pub t_pub_ns: u64, pub publisher: u32, pub msg_size: u32
 pub struct gs_msg_summary {
     pub delivered: u64, pub lat_sum_ms: u64, pub p50_ms: u32, pub p95_ms: u32, pub max_ms: u32,
     pub reserved: u32, pub hist: [u32; GS_HIST_BINS],
+}
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct gs_peer_delay {
+    pub completed: u64, pub delay_sum_ms: u64, pub last_rx_ns: u64, pub last_ms: u32, pub reserved: u32,
+    pub bucket: [u64; GS_DELAY_BUCKETS + 1],
 }
 pub type gs_block_fn = Option<unsafe extern "C" fn(user: *mut c_void, first_msg: u64, n_msgs: u32, peers: u32,
                                                    t_complete_ns: *const u64, hops: *const u8)>;
@@ -137,6 +143,14 @@ extern "C" {
     pub fn gs_set_timing(ctx: *mut gs_ctx, enable: u32) -> gs_status;
     pub fn gs_set_traffic(ctx: *mut gs_ctx, enable: u32) -> gs_status;
     pub fn gs_get_traffic(ctx: *mut gs_ctx, traffic: *mut u64) -> gs_status;
+    pub fn gs_set_peer_delay(ctx: *mut gs_ctx, enable: u32) -> gs_status;
+    pub fn gs_get_peer_delay(ctx: *mut gs_ctx, out: *mut gs_peer_delay) -> gs_status;
+    pub fn gs_reset_peer_delay(ctx: *mut gs_ctx) -> gs_status;
+    pub fn gs_peer_delay_add_lat(ctx: *mut gs_ctx, sched: *const gs_publish, n_msgs: u64,
+                                 lat_ms: *const u16) -> gs_status;
+    pub fn gs_write_testnode_metrics(cfg: *const gs_config, path: *const c_char, row_ptr: *const u64,
+                                     mesh_count: *const u8, sched: *const gs_publish, n_msgs: u64,
+                                     delay: *const gs_peer_delay) -> gs_status;
     pub fn gs_get_config(ctx: *const gs_ctx, out: *mut gs_config) -> gs_status;
     pub fn gs_save_state(ctx: *mut gs_ctx, path: *const c_char) -> gs_status;
     pub fn gs_load_state(path: *const c_char, device: i32, out: *mut *mut gs_ctx) -> gs_status;
