@@ -241,18 +241,24 @@ extern "C" gs_status gs_get_mesh(gs_ctx* ctx, uint32_t* mesh, uint8_t* count) {
   GS_API_END(ctx)
 }
 
+// What gs_run and gs_run_partitioned accept of a sink (sink may be NULL); the error leaves through c.
+void gs::check_sink(Ctx& c, const gs_result_sink* sink) {
+  if (!sink) return;
+  if (sink->on_block && (sink->t_complete_ns || sink->hops))
+    c.fail(GS_EINVAL, "gs_result_sink: with on_block, t_complete_ns and hops must be NULL (select outputs "
+                      "with want, ABI 7)");
+  if (sink->want & ~(uint32_t)(GS_WANT_T_COMPLETE | GS_WANT_HOPS | GS_WANT_LAT_MS))
+    c.fail(GS_EINVAL, "gs_result_sink.want: unknown bits");
+  if ((sink->on_lat != nullptr) != ((sink->want & GS_WANT_LAT_MS) != 0))
+    c.fail(GS_EINVAL, "gs_result_sink: on_lat and GS_WANT_LAT_MS go together");
+}
+
 extern "C" gs_status gs_run(gs_ctx* ctx, const gs_publish* sched, uint64_t n_msgs,
                             const gs_result_sink* sink) {
   GS_API_BEGIN(ctx)
   if (!ctx->mesh_built) ctx->fail(GS_ESTATE, "gs_mesh_converge first");
   if (!sched && n_msgs) ctx->fail(GS_EINVAL, "null schedule");
-  if (sink && sink->on_block && (sink->t_complete_ns || sink->hops))
-    ctx->fail(GS_EINVAL, "gs_result_sink: with on_block, t_complete_ns and hops must be NULL (select outputs "
-                         "with want, ABI 7)");
-  if (sink && (sink->want & ~(uint32_t)(GS_WANT_T_COMPLETE | GS_WANT_HOPS | GS_WANT_LAT_MS)))
-    ctx->fail(GS_EINVAL, "gs_result_sink.want: unknown bits");
-  if (sink && (sink->on_lat != nullptr) != ((sink->want & GS_WANT_LAT_MS) != 0))
-    ctx->fail(GS_EINVAL, "gs_result_sink: on_lat and GS_WANT_LAT_MS go together");
+  check_sink(*ctx, sink);
   if (ctx->pdelay && ctx->part_parts > 1)  // (the accumulators cover the partition's rows, gs_run all peers)
     ctx->fail(GS_EUNSUPPORTED, "gs_run with gs_set_peer_delay on a partitioned context: use gs_run_partitioned");
   GS_HIP(hipSetDevice(ctx->cfg.device));
@@ -264,18 +270,6 @@ extern "C" gs_status gs_run(gs_ctx* ctx, const gs_publish* sched, uint64_t n_msg
 // streaming sink — so the schedule order is kept (class_plan), every completion path writes
 // the u16 latencies and no batch runs without its log — whose on_lat is never called:
 // while ctx->text.fn is set, deliver hands each batch's latencies to the formatter.
-static void text_sink_unused(void*, uint64_t, uint32_t, uint32_t, const uint16_t*) {}
-struct TextCall {
-  gs_ctx* c;
-  TextCall(gs_ctx* ctx, const gs_publish* sched, gs_text_fn fn, void* user, uint64_t chunk) : c(ctx) {
-    c->text.fn = fn;
-    c->text.user = user;
-    c->text.chunk = chunk;
-    c->text.sched = sched;
-  }
-  ~TextCall() { c->text = Ctx::TextRun{}; }
-};
-
 extern "C" gs_status gs_run_log(gs_ctx* ctx, const gs_publish* sched, uint64_t n_msgs, gs_text_fn on_text,
                                 void* user, uint64_t chunk_bytes) {
   GS_API_BEGIN(ctx)

@@ -359,13 +359,42 @@ struct Ctx {
   // stats
   gs_stats stats{};
   std::vector<hipEvent_t> ev_pool;
-  size_t ev_n = 0;  // timing: the cursor of the run in progress into ev_pool (gs_relax.hip run_ev)
+  size_t ev_n = 0;  // timing: the cursor of the run in progress into ev_pool (run_ev below)
   int num_cus = 0;
   std::string gossip_why;  // the message that broke the last partitioned gossip no-op proof
 
   ~Ctx();
   void fail(gs_status c, const std::string& m) { throw Error(c, m); }
 };
+
+// Timing events come from a per-context pool: [0] run start, [1] run end, then
+// one (start, scan end, end) triple around every relaxation launch; c.ev_n is
+// the cursor of the run in progress (Run, gs_run.h; PRun, gs_prun.h).
+inline hipEvent_t run_ev(Ctx& c, size_t i) {
+  while (c.ev_pool.size() <= i) {
+    hipEvent_t e;
+    GS_HIP(hipEventCreate(&e));
+    c.ev_pool.push_back(e);
+  }
+  return c.ev_pool[i];
+}
+
+// The arrival log as text: Ctx::text holds the callback for the length of one call
+// (gs_run_log, gs_format_lat_log, gs_run_partitioned_log), whose latency-only sink's
+// on_lat is never called.
+inline void text_sink_unused(void*, uint64_t, uint32_t, uint32_t, const uint16_t*) {}
+struct TextCall {
+  Ctx* c;
+  TextCall(Ctx* ctx, const gs_publish* sched, gs_text_fn fn, void* user, uint64_t chunk) : c(ctx) {
+    c->text.fn = fn;
+    c->text.user = user;
+    c->text.chunk = chunk;
+    c->text.sched = sched;
+  }
+  TextCall(const TextCall&) = delete;
+  ~TextCall() { c->text = Ctx::TextRun{}; }
+};
+void check_sink(Ctx& c, const gs_result_sink* sink);  // gs_ctx.hip: gs_run's rules for a sink
 
 // ---- launchers (gs_topology.hip / gs_mesh.hip / gs_relax.hip) ----
 void launch_topology(Ctx& c);
@@ -404,7 +433,7 @@ uint64_t part_begin(Ctx& c, const gs_publish* sched, uint64_t n_msgs);
 bool part_scan(Ctx& c, uint64_t bucket_key, gs_part_record* rec, uint64_t cap, uint64_t* n, uint64_t* m1);
 uint64_t part_relax(Ctx& c, uint64_t bucket_key, const gs_part_record* rec, uint64_t n);
 void part_finish(Ctx& c, const gs_result_sink* sink);
-// device-driven partitioned protocol (gs_comm.hip)
+// device-driven partitioned protocol (gs_prun.h)
 void part_dev_bucket(Ctx& c, uint32_t parts);
 void part_dev_scan_count(Ctx& c, uint32_t parts);
 void part_dev_export(Ctx& c, uint32_t parts, gs_part_record* out);

@@ -1,6 +1,6 @@
 // gs_layout.h — the partition arithmetic of gs_run_partitioned,
-// shared by the loop-back and the RCCL branches of gs_comm.hip so that both
-// move the same blocks. Host-only, no HIP: tests/test_host_cpu.py compiles it
+// shared by the loop-back and the rank bodies of gs_prun.h's exchanges so that
+// both move the same blocks. Host-only, no HIP: tests/test_host_cpu.py compiles it
 // with g++ and checks the exchanges for uneven splits and B < P on the CPU.
 #pragma once
 #include <stdint.h>

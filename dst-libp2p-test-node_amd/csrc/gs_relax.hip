@@ -968,17 +968,6 @@ static void collect_stats(Ctx& c) {
 }
 
 
-// Timing events come from a per-context pool: [0] run start, [1] run end, then
-// one (start, scan end, end) triple around every relaxation launch; c.ev_n is
-// the cursor of the run in progress (Run, gs_run.h).
-static hipEvent_t run_ev(Ctx& c, size_t i) {
-  while (c.ev_pool.size() <= i) {
-    hipEvent_t e;
-    GS_HIP(hipEventCreate(&e));
-    c.ev_pool.push_back(e);
-  }
-  return c.ev_pool[i];
-}
 // One pass of the pull or list path, under timing as (start, mid, end): the whole pass is frontier time.
 template <class Fn>
 static void timed_pass(Ctx& c, hipStream_t s, Fn&& launch) {

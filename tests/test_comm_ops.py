@@ -17,6 +17,7 @@ protocol, and a churn batch (message-sharded)."""
 import os
 import socket
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -161,3 +162,57 @@ def test_run_partitioned_across_processes_equals_gs_run(tmp_path, name, world):
         assert all(p["st"][2] == 0 for p in parts)
     if name == "churn":
         assert all(p["st"][3] > 0 for p in parts)  # message-sharded batches
+
+
+FAIL_N, FAIL_M = 601, 6
+
+
+def _fail_sched():
+    import gossipsim
+    t = gossipsim.T0_NS + np.arange(FAIL_M, dtype=np.uint64) * np.uint64(1_000_000_000)
+    return t, (6 + 7 * np.arange(FAIL_M)) % FAIL_N, np.full(FAIL_M, 15000)
+
+
+def _fail_worker(rank, world, port, outdir):
+    _setup(rank, world, port)
+    import gossipsim
+    sched = _fail_sched()
+    sim = _sim(dict(peers=FAIL_N, batch=FAIL_M, seed=72))
+    comm = gossipsim.Comm(nranks=world, rank=rank, device=0, transport=gossipsim.TorchDistTransport())
+    sim.set_traffic(rank == 1)  # per-peer traffic: the one knob a partitioned batch's set-up refuses
+    try:
+        comm.run_partitioned([sim], sched)
+        why = "no error"
+    except gossipsim.GossipSimError as e:
+        why = str(e)
+    sim.set_traffic(False)
+    (r,) = comm.run_partitioned([sim], sched)  # the context and the communicator take a good run
+    np.savez(os.path.join(outdir, "r%d.npz" % rank), why=np.array(why), tc=r["t_complete"], hops=r["hops"])
+    comm.close()
+    sim.close()
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.gpu
+def test_run_partitioned_rank_failing_setup_takes_the_others_out(tmp_path):
+    """A rank whose batch set-up fails (here: rank 1 alone counts per-peer
+    traffic) fails with its own error, and the other rank fails the call too
+    instead of waiting for it in the next collective: an error return on the
+    host of both, after which both contexts take a good run. The ranks are
+    joined under a deadline, so ranks left waiting on each other fail the test."""
+    world = 2
+    ctx = mp.spawn(_fail_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=False)
+    deadline = time.monotonic() + 120
+    while not ctx.join(timeout=max(0.0, deadline - time.monotonic())):
+        if time.monotonic() >= deadline:
+            for p in ctx.processes:
+                p.kill()
+            pytest.fail("the ranks wait on each other")
+    parts = [np.load(os.path.join(tmp_path, "r%d.npz" % r)) for r in range(world)]
+    why = [str(p["why"]) for p in parts]
+    assert "GS_EUNSUPPORTED" in why[1] and "per-peer traffic" in why[1]
+    assert "GS_EINVAL" in why[0] and "another rank failed" in why[0]
+    ref = _sim(dict(peers=FAIL_N, batch=FAIL_M, seed=72)).run(_fail_sched())
+    np.testing.assert_array_equal(np.concatenate([p["tc"] for p in parts], axis=1), ref["t_complete"])
+    np.testing.assert_array_equal(np.concatenate([p["hops"] for p in parts], axis=1), ref["hops"])

@@ -318,6 +318,83 @@ def test_run_partitioned_rccl_message_sharded(monkeypatch, piece):
     assert st[0]["ms_batches"] == 1
 
 
+@pytest.mark.parametrize("push", [False, True])
+def test_run_partitioned_timing(monkeypatch, push):
+    """gs_set_timing on a partitioned run (loop-back, P = 3, uneven parts): the
+    rows stay gs_run's bit for bit; the push protocol books every bucket's scan
+    and frontier time and their sum as relax time on every part, the list pass
+    books its passes as frontier time alone."""
+    if push:
+        monkeypatch.setenv("GS_PART_PUSH", "1")
+    N, M, parts = 2003, 8, 3
+    p = oracle.params(peers=N, seed=67)
+    sched = _sched(M, N)
+    ref, _ = _whole(p, 5, (50, 150, 40, 130), sched, M)
+    sims = _parts(p, 5, (50, 150, 40, 130), parts, M)
+    for s in sims:
+        s.set_timing(True)
+        s.reset_stats()
+    comm = gossipsim.Comm(local_parts=parts)
+    res = comm.run_partitioned(sims, sched)
+    np.testing.assert_array_equal(np.concatenate([r["t_complete"] for r in res], axis=1), ref["t_complete"])
+    np.testing.assert_array_equal(np.concatenate([r["hops"] for r in res], axis=1), ref["hops"])
+    for x in (s.stats() for s in sims):
+        assert (x["list_pull_batches"] > 0) != push
+        if push:
+            assert x["scan_ms"] > 0 and x["frontier_ms"] > 0
+            assert x["relax_ms"] == pytest.approx(x["scan_ms"] + x["frontier_ms"], rel=1e-9)
+        else:
+            assert x["scan_ms"] == 0
+            assert x["frontier_ms"] > 0 and x["frontier_ms"] == x["relax_ms"]
+    comm.close()
+
+
+def test_run_partitioned_gossip_iwants_from_push(monkeypatch):
+    """The gossip fallback out of the push protocol (GS_PART_PUSH; a heartbeat at
+    the publish instant): push's eager result is discarded, counters restored,
+    and every batch runs message-sharded with gossip; bit-exact against gs_run
+    and the oracle, IWANTs counted."""
+    monkeypatch.setenv("GS_PART_PUSH", "1")
+    N = 2003
+    p = oracle.params(peers=N, seed=60, lazy_gossip=1, hb_phase_ns=T0 % 1_000_000_000)
+    st, rst = _ms_check(p, 5, (50, 150, 40, 130), 3, _sched(8, N), 4)
+    assert rst["gossip_iwant"] > 0
+    assert all(x["ms_batches"] == 2 and x["gossip_fallback_batches"] >= 2 for x in st)
+
+
+def test_run_partitioned_argument_rules():
+    """What gs_run_partitioned refuses before or inside the first batch, each an
+    error return that leaves the contexts usable: a context count that is not
+    the communicator's parts, a part without a mesh, parts of unequal batch, and
+    a per-message summary of a message-sharded batch."""
+    N = 300
+    p = oracle.params(peers=N, seed=57)
+    sched = _sched(4, N)
+    sims = _parts(p, 1, (50, 50, 50, 50), 2, 4)
+    comm = gossipsim.Comm(local_parts=2)
+    with pytest.raises(gossipsim.GossipSimError, match="GS_EINVAL.*one context per part"):
+        comm.run_partitioned(sims[:1], sched)
+    kw = {n: getattr(p, n) for n, _ in oracle.OrParams._fields_}
+    kw["batch"] = 4
+    bare = gossipsim.Simulator(**kw)
+    with pytest.raises(gossipsim.GossipSimError, match="GS_ESTATE.*gs_mesh_converge first"):
+        comm.run_partitioned([sims[0], bare], sched)
+    (other,) = _parts(p, 1, (50, 50, 50, 50), 1, 8)
+    with pytest.raises(gossipsim.GossipSimError, match="GS_EINVAL.*same peers and batch"):
+        comm.run_partitioned([sims[0], other], sched)
+    res = comm.run_partitioned(sims, sched)
+    ref, _ = _whole(p, 1, (50, 50, 50, 50), sched, 4)
+    np.testing.assert_array_equal(np.concatenate([r["t_complete"] for r in res], axis=1), ref["t_complete"])
+    pc = oracle.params(peers=N, seed=57, churn_ppm=20000, hb_phase_ns=gossipsim.SHADOW_START_NS)
+    csims = _parts(pc, 1, (50, 50, 50, 50), 2, 4)
+    with pytest.raises(gossipsim.GossipSimError, match="GS_EUNSUPPORTED.*per-message summaries"):
+        comm.run_partitioned(csims, sched, summary=True)
+    res = comm.run_partitioned(csims, sched)
+    ref, _ = _whole(pc, 1, (50, 50, 50, 50), sched, 4)
+    np.testing.assert_array_equal(np.concatenate([r["t_complete"] for r in res], axis=1), ref["t_complete"])
+    comm.close()
+
+
 def test_run_partitioned_refuses_traffic():
     """Per-peer traffic is the one knob partitioned mode refuses."""
     p = oracle.params(peers=600, seed=60)
