@@ -323,6 +323,7 @@ extern "C" gs_status gs_reset_stats(gs_ctx* ctx) {
   GS_HIP(hipMemsetAsync(ctx->d_counters.p, 0, C_COUNT * 8, ctx->stream));
   if (ctx->traffic)
     GS_HIP(hipMemsetAsync(ctx->d_traffic.p, 0, (size_t)ctx->cfg.peers * GS_TRAFFIC_COLS * 8, ctx->stream));
+  pubsub_reset(*ctx);
   GS_HIP(hipStreamSynchronize(ctx->stream));
   memset(&ctx->stats, 0, sizeof(ctx->stats));
   // (glp_prefer, the path choice learnt from a failed no-op proof, is no statistic: it
@@ -355,6 +356,31 @@ extern "C" gs_status gs_get_traffic(gs_ctx* ctx, uint64_t* traffic) {
   GS_HIP(hipSetDevice(ctx->cfg.device));
   GS_HIP(hipMemcpyAsync(traffic, ctx->d_traffic.p, (size_t)ctx->cfg.peers * GS_TRAFFIC_COLS * 8,
                         hipMemcpyDeviceToHost, ctx->stream));
+  GS_HIP(hipStreamSynchronize(ctx->stream));
+  GS_API_END(ctx)
+}
+
+// ---- per-peer pubsub event counters (gs_pubsub.h) ----
+extern "C" gs_status gs_set_pubsub_counts(gs_ctx* ctx, uint32_t enable) {
+  GS_API_BEGIN(ctx)
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  pubsub_set(*ctx, enable != 0);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_get_pubsub_counts(gs_ctx* ctx, uint64_t* out) {
+  GS_API_BEGIN(ctx)
+  if (!out) ctx->fail(GS_EINVAL, "null pubsub counts array");
+  if (!ctx->pubsub) ctx->fail(GS_ESTATE, "gs_set_pubsub_counts(ctx, 1) first");
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  pubsub_get(*ctx, out);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_reset_pubsub_counts(gs_ctx* ctx) {
+  GS_API_BEGIN(ctx)
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  pubsub_reset(*ctx);
   GS_HIP(hipStreamSynchronize(ctx->stream));
   GS_API_END(ctx)
 }

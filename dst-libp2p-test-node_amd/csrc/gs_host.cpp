@@ -665,8 +665,9 @@ extern "C" gs_status gs_write_node_metrics(const gs_config* cfg, const char* pat
 // format: "# HELP" (the node's help strings verbatim) and "# TYPE" per family, then
 // one series per peer labelled muxer and peer_id. The node's peer_id is its libp2p
 // PeerId; pod-<id> stands in for it (the host names of gs_write_node_metrics).
-// dst_testnode_received_chunks_total (main.nim:37-41) is not written: it counts
-// fragment first arrivals, which completion does not keep per peer.
+// dst_testnode_received_chunks_total (main.nim:37-41) is not written here: it counts
+// fragment first arrivals, which completion does not keep per peer
+// (gs_write_pubsub_metrics writes it from the event counters).
 extern "C" gs_status gs_write_testnode_metrics(const gs_config* cfg, const char* path, const uint64_t* row_ptr,
                                                const uint8_t* mesh_count, const gs_publish* sched, uint64_t n_msgs,
                                                const gs_peer_delay* delay) {
@@ -724,6 +725,42 @@ extern "C" gs_status gs_write_testnode_metrics(const gs_config* cfg, const char*
          [&](uint32_t u) { return (uint64_t)mesh_count[u]; });
   family("dst_testnode_topic_peers", "gauge", "current number of GossipSub peers for the test topic",
          [&](uint32_t u) { return row_ptr[u + 1] - row_ptr[u]; });
+  if (fclose(f)) return GS_EINVAL;
+  return GS_OK;
+}
+
+// The go node's pubsub counters (go-test-node/metrics.go:84-220: names with their _total,
+// help strings verbatim, the topic label where the node's family has one) and the nim
+// node's dst_testnode_received_chunks_total (main.nim:37-41) from the per-peer event
+// counts (gs_get_pubsub_counts), in the Prometheus text exposition format.
+extern "C" gs_status gs_write_pubsub_metrics(const gs_config* cfg, const char* path, uint32_t peers,
+                                             const uint64_t* counts) {
+  if (!cfg || !path || !counts) return GS_EINVAL;
+  if (cfg->muxer > GS_MUX_MPLEX) return GS_EINVAL;
+  FILE* f = fopen(path, "w");
+  if (!f) return GS_EINVAL;
+  std::vector<char> buf(1 << 20);
+  setvbuf(f, buf.data(), _IOFBF, buf.size());
+  auto family = [&](const char* name, const char* help, bool topic, int col) {
+    fprintf(f, "# HELP %s %s\n# TYPE %s counter\n", name, help, name);
+    for (uint32_t u = 0; u < peers; u++)
+      fprintf(f, "%s{%speer_id=\"pod-%u\"} %llu\n", name, topic ? "topic=\"test\"," : "", u,
+              (unsigned long long)counts[(size_t)u * GS_PUBSUB_COLS + col]);
+  };
+  family("libp2p_pubsub_broadcast_messages_total", "pubsub broadcast messages", true, GS_PS_MSG_TX);
+  family("libp2p_pubsub_received_messages_total", "pubsub received messages", true, GS_PS_MSG_RX);
+  family("libp2p_pubsub_broadcast_ihave_total", "pubsub broadcast ihave", true, GS_PS_IHAVE_TX);
+  family("libp2p_pubsub_received_ihave_total", "pubsub received ihave", true, GS_PS_IHAVE_RX);
+  family("libp2p_pubsub_broadcast_iwant_total", "pubsub broadcast iwant", false, GS_PS_IWANT_TX);
+  family("libp2p_pubsub_received_iwant_total", "pubsub received iwant", false, GS_PS_IWANT_RX);
+  family("libp2p_gossipsub_received_total", "number of messages received (deduplicated)", false, GS_PS_FIRST);
+  family("libp2p_gossipsub_duplicate_total", "number of duplicates received", false, GS_PS_DUP);
+  static const char* const kMux[3] = {"yamux", "quic", "mplex"};
+  const char* chunks = "dst_testnode_received_chunks_total";
+  fprintf(f, "# HELP %s number of application-level message chunks received\n# TYPE %s counter\n", chunks, chunks);
+  for (uint32_t u = 0; u < peers; u++)
+    fprintf(f, "%s{muxer=\"%s\",peer_id=\"pod-%u\"} %llu\n", chunks, kMux[cfg->muxer], u,
+            (unsigned long long)counts[(size_t)u * GS_PUBSUB_COLS + GS_PS_FIRST]);
   if (fclose(f)) return GS_EINVAL;
   return GS_OK;
 }

@@ -105,6 +105,11 @@ struct Ctx {
   bool timing = false;
   bool traffic = false;        // gs_set_traffic: per-peer send/receive counters
   DevBuf<uint64_t> d_traffic;  // [N][GS_TRAFFIC_COLS]
+  bool pubsub = false;         // gs_set_pubsub_counts (gs_pubsub.h): per-peer event counters
+  DevBuf<uint64_t> d_pubsub;   // [N][GS_PUBSUB_COLS]
+  // A pass over the finished batch's dense final keys follows (either switch): the run plan
+  // keeps dense rows and the churn ring's ELL snapshots, and takes no path without them.
+  bool keys_pass() const { return traffic || pubsub; }
   // gs_set_peer_delay (gs_peerdelay.h): per-peer delay accumulators of the context's own rows
   bool pdelay = false;
   DevBuf<uint64_t> d_pdelay;   // [PD_COLS][own rows]
@@ -424,6 +429,9 @@ void deliver_rows(Ctx& c, uint32_t B, uint32_t un, const gs_result_sink* sink, u
 void format_lat_log(Ctx& c, const gs_publish* sched, uint64_t n_msgs, const uint16_t* lat_ms);
 void log_text_reset(Ctx& c);
 // per-peer delay accumulators (gs_peerdelay.h)
+void pubsub_set(Ctx& c, bool on);
+void pubsub_reset(Ctx& c);
+void pubsub_get(Ctx& c, uint64_t* out);
 void peer_delay_set(Ctx& c, bool on);
 void peer_delay_reset(Ctx& c);
 void peer_delay_get(Ctx& c, gs_peer_delay* out);

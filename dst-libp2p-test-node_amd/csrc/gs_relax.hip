@@ -908,6 +908,11 @@ static RelaxArgs relax_args(Ctx& c, const Batch& b, bool gossip) {
   return ra;
 }
 
+// The grid of a grid-stride pass over a finished batch's `total` dense keys.
+static unsigned keys_pass_grid(const Ctx& c, uint64_t total) {
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + TB - 1) / TB, (uint64_t)c.num_cus * 8));
+}
+
 // Per-peer traffic of the batch just finished (keys final, before the next
 // reset; gs_traffic.h).
 static void launch_traffic(Ctx& c, const Batch& b) {
@@ -925,8 +930,7 @@ static void launch_traffic(Ctx& c, const Batch& b) {
   ta.flood = c.cfg.flood_publish;
   ta.collide = b.collide ? 1 : 0;
   hipStream_t s = c.stream;
-  const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((ra.total + TB - 1) / TB,
-                                                                           (uint64_t)c.num_cus * 8));
+  const unsigned grid = keys_pass_grid(c, ra.total);
   k_traffic_pub<<<b.B, TB, 0, s>>>(ra, ta);
 #define GS_TRAFFIC(FPV)                                                    \
   k_traffic_fwd<FPV><<<grid, TB, 0, s>>>(ra, ta);                          \
@@ -941,6 +945,8 @@ static void launch_traffic(Ctx& c, const Batch& b) {
 #undef GS_TRAFFIC
   GS_HIP(hipGetLastError());
 }
+
+#include "gs_pubsub.h"
 
 // Read the device counters into ctx->stats (and raise the device error word).
 static void collect_stats(Ctx& c) {

@@ -96,14 +96,15 @@ static Batch with_window(const Batch& b, uint64_t w) {
   return x;
 }
 
-// Dense rows: a sink's rows or summaries, the traffic pass, GS_LPULL_DENSE (diagnostic:
+// Dense rows: a sink's rows or summaries, a pass over the final keys (Ctx::keys_pass:
+// per-peer traffic or pubsub counts), GS_LPULL_DENSE (diagnostic:
 // dense rows + k_complete, whose known key stream calibrates the PMC read factor,
 // scripts/pmc_summary.py). IDONTWANT batches keep their final keys dense all along
 // and ask for no conversion: run_lpull_batch never looks at `dense` under IDONTWANT, so
 // the in-pass gossip, which used to pass it regardless, shares the rule. (Slice groups
-// refuse per-peer traffic up front: the traffic term is false there.)
+// refuse such a pass up front: the keys_pass term is false there.)
 static bool dense_rows(const Ctx& c, const SinkWants& sw, bool idw) {
-  return !idw && (sw.rows() || sw.summary || c.traffic || getenv("GS_LPULL_DENSE"));
+  return !idw && (sw.rows() || sw.summary || c.keys_pass() || getenv("GS_LPULL_DENSE"));
 }
 
 // Lazy gossip inside the list pass (GOS, gs_lpull_kernel.h), on top of the list
@@ -313,7 +314,7 @@ struct AsyncOff {
 // GS_CHN_PIPE=0 keeps one stream (GS_PASS_XCDS alone then still moves the passes).
 static bool chain_pipe_wanted(Ctx& c) {
   ensure_cus(c);
-  return c.cfg.churn_ppm && !env_off("GS_CHN_PIPE") && c.num_cus == 256 && c.cfg.flood_publish && !c.traffic &&
+  return c.cfg.churn_ppm && !env_off("GS_CHN_PIPE") && c.num_cus == 256 && c.cfg.flood_publish && !c.keys_pass() &&
          !c.sink_dev && !getenv("GS_DEBUG_CHN");
 }
 // c.stream is the passes' stream for the run; the caller's stream waits for it at the end.
@@ -698,7 +699,7 @@ struct Run {
 
   // The group from i0, if there is one: at least two full batches of i0's shape.
   bool form_slices(uint64_t i0, SliceGroup& G) {
-    if (sl_max < 2 || !pull_any || c.traffic || (uint64_t)N * 2 >= (1u << 21)) return false;
+    if (sl_max < 2 || !pull_any || c.keys_pass() || (uint64_t)N * 2 >= (1u << 21)) return false;
     const uint32_t F0 = frags_of(c, sched[i0]);
     if (!list_pass_any(pow2_at_least(F0))) return false;
     const uint32_t Bc = pull_batch_cap(Bmax, F0);
@@ -936,7 +937,7 @@ struct Run {
   }
 
   void complete(const BatchRun& r) {
-    if (c.traffic) launch_traffic(c, r.b);
+    if (c.keys_pass()) launch_key_passes(c, r.b);
     launch_complete(c, r.b, 0, N, sink, r.i0);
   }
 
@@ -967,7 +968,7 @@ struct Run {
       }
       // readers of the ELL snapshots beside the list pass: seeds to the mesh (no flood
       // publish), the per-peer traffic pass, the GS_DEBUG_CHN check
-      if (chn && (!c.cfg.flood_publish || c.traffic || getenv("GS_DEBUG_CHN"))) ensure_ring_ell(c, h_lo, h_end);
+      if (chn && (!c.cfg.flood_publish || c.keys_pass() || getenv("GS_DEBUG_CHN"))) ensure_ring_ell(c, h_lo, h_end);
       //  a batch for the push path may overlap the last epochs of an
       // earlier churn list-pass batch, which skipped their ELL snapshots and
       // inverse IHAVE lists: rebuild those slots (tag-checked: free when current)
@@ -1138,7 +1139,7 @@ struct Run {
 
   // Without lazy gossip the eager result is the batch's.
   bool finish_eager(const BatchRun& r) {
-    if (c.traffic) launch_traffic(c, r.b);
+    if (c.keys_pass()) launch_key_passes(c, r.b);
     if (!r.nl.on) launch_complete(c, r.b, 0, N, sink, r.i0);  // (a no-log batch: the passes completed it)
     return true;
   }
@@ -1166,7 +1167,7 @@ struct Run {
       noop = bsum ? ms[0] == (uint64_t)B * (N - 1) && ms[1] < rel0[0] + b.lat_min : gossip_noop(b, ms.data(), rel0);
     }
     if (noop) {
-      if (c.traffic) launch_traffic(c, b);
+      if (c.keys_pass()) launch_key_passes(c, b);
       deliver(c, b, 0, N, sink, r.i0);
       c.stats.gossip_noop_msgs += B;
       return true;

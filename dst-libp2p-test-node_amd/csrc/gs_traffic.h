@@ -18,6 +18,20 @@
 // receiver's rx columns and the receiver returns ceil(packets / 2) pure ACKs
 // (the ctrl columns). These passes only read the keys; the counters take
 // atomics (diagnostic mode, off by default).
+//
+// The enumeration exists once: sends_pub / sends_fwd<FP> / sends_gossip<FP> are
+// the bodies, parameterised by an accumulation policy P that says what a send,
+// an arrival and a first receipt add. TrafficAcc (here) adds bytes, packets and
+// ACKs; PubsubAcc (gs_pubsub.h) adds event counts. A policy gives
+//   P::Args   the kernel argument (Fe, flood, collide and its counters)
+//   P::Peer   one peer's counts in registers: data_tx(t, n), data_acked(t, n),
+//             data_rx(t), ihave_tx(t), ihave_acked(t), iwant_tx(t), iwant_rx(t),
+//             iwant_acked(t), flush(t, x)
+//   P::data_arrive(t, x), P::ihave_arrive(t, x)   one arrival at another peer x
+//   P::published(t, p), P::completed(t, u)        (P::completions: the reassembly test runs)
+//   P::first(t, f, valid, u, base, L, lane)       the lane's own first receipt (wave-uniform call)
+// The kernels are thin __global__ wrappers, so a policy's empty hooks cost the
+// other policy's kernels nothing.
 
 struct TrafficArgs {
   uint64_t* traffic;        // [N][GS_TRAFFIC_COLS]
@@ -58,14 +72,36 @@ __device__ __forceinline__ void tr_count(const TrafficArgs& t, uint32_t x, int c
   atomicAdd((unsigned long long*)&t.traffic[(size_t)x * GS_TRAFFIC_COLS + col], 1ull);
 }
 
+// What gs_set_traffic accumulates of the enumeration below.
+struct TrafficAcc {
+  using Args = TrafficArgs;
+  struct Peer : PeerTraffic {
+    __device__ void data_tx(const Args& t, uint64_t n) { send(n, t.W, t.pk, t.hdr); }
+    __device__ void data_acked(const Args& t, uint64_t n) { acked(n, t.pk); }
+    __device__ void data_rx(const Args& t) { recv(1, t.W, t.pk, t.hdr); }
+    __device__ void ihave_tx(const Args& t) { send(1, t.ihw, t.ihpk, t.ihhd); }
+    __device__ void ihave_acked(const Args& t) { acked(1, t.ihpk); }
+    __device__ void iwant_tx(const Args& t) { send(1, t.iww, t.iwpk, t.iwhd); }
+    __device__ void iwant_rx(const Args& t) { recv(1, t.iww, t.iwpk, t.iwhd); }
+    __device__ void iwant_acked(const Args& t) { acked(1, t.iwpk); }
+  };
+  static constexpr bool completions = true;
+  static __device__ __forceinline__ void data_arrive(const Args& t, uint32_t x) { tr_arrive(t, x, t.W, t.pk, t.hdr); }
+  static __device__ __forceinline__ void ihave_arrive(const Args& t, uint32_t x) { tr_arrive(t, x, t.ihw, t.ihpk, t.ihhd); }
+  static __device__ __forceinline__ void published(const Args& t, uint32_t p) { tr_count(t, p, GS_TR_PUBLISHED); }
+  static __device__ __forceinline__ void completed(const Args& t, uint32_t u) { tr_count(t, u, GS_TR_RECEIVED); }
+  static __device__ __forceinline__ void first(const Args&, bool, bool, uint32_t, uint64_t, uint32_t, int) {}
+};
+
 // Publishes (publish_new_message, main.rs:101-143): one block per message.
-__global__ __launch_bounds__(TB) void k_traffic_pub(RelaxArgs a, TrafficArgs t) {
+template <class P>
+__device__ __forceinline__ void sends_pub(const RelaxArgs& a, const typename P::Args& t) {
   __shared__ uint32_t live[MAX_DEG];
   __shared__ uint32_t wcnt[TB / 64];
   const uint32_t m = blockIdx.x, p = a.pub[m], sp = a.stage[p], S = a.S;
   const uint64_t ser = a.tables[S * S + sp];
   if (a.churn && ep_off(a, a.q0[m], p)) return;  // offline publisher: nothing published
-  if (threadIdx.x == 0) tr_count(t, p, GS_TR_PUBLISHED);
+  if (threadIdx.x == 0) P::published(t, p);
   uint32_t deg;
   const uint32_t* tg;
   bool packed;
@@ -91,7 +127,7 @@ __global__ __launch_bounds__(TB) void k_traffic_pub(RelaxArgs a, TrafficArgs t) 
     deg = tot;
     tg = live;
   }
-  PeerTraffic pt;
+  typename P::Peer pt;
   const uint32_t total = t.Fe * deg;
   for (uint32_t i = threadIdx.x; i < total; i += TB) {
     const uint32_t f = i / deg, j = i % deg;
@@ -99,18 +135,19 @@ __global__ __launch_bounds__(TB) void k_traffic_pub(RelaxArgs a, TrafficArgs t) 
     const uint32_t sw = a.stage[w];
     const uint64_t sd = a.tables[S * S + S + sw];
     const uint64_t arr = ((uint64_t)f * deg + j + 1) * ser + a.tables[sp * S + sw] + (sd > ser ? sd - ser : 0);
-    pt.send(1, t.W, t.pk, t.hdr);
+    pt.data_tx(t, 1);
     if (a.churn && ev_lost(a, m, arr, w)) continue;
-    tr_arrive(t, w, t.W, t.pk, t.hdr);
-    pt.acked(1, t.pk);
+    P::data_arrive(t, w);
+    pt.data_acked(t, 1);
   }
   pt.flush(t, p);
 }
+__global__ __launch_bounds__(TB) void k_traffic_pub(RelaxArgs a, TrafficArgs t) { sends_pub<TrafficAcc>(a, t); }
 
 // Forwards and completions: one lane per key (u, m, f); a wave holds whole
 // FP-lane groups, so the uplink FIFO fold runs as in relax_lane.
-template <int FP>
-__global__ __launch_bounds__(TB) void k_traffic_fwd(RelaxArgs a, TrafficArgs t) {
+template <class P, int FP>
+__device__ __forceinline__ void sends_fwd(const RelaxArgs& a, const typename P::Args& t) {
   const int lane = threadIdx.x & 63;
   const uint32_t S = a.S, LL = a.L;
   const uint64_t smask = (1ull << a.sb) - 1;
@@ -124,11 +161,13 @@ __global__ __launch_bounds__(TB) void k_traffic_fwd(RelaxArgs a, TrafficArgs t) 
     const uint32_t m = slot / FP, fl = slot & (FP - 1);
     const uint32_t pm = valid ? a.pub[m] : EMPTY;
     const bool got = key != INF64 && u != pm;
-    {  // completed messages (reassembly, main.rs:79-99): every fragment of the group received
+    P::first(t, got && fl < t.Fe, valid, u, base, LL, lane);
+    // completed messages (reassembly, main.rs:79-99): every fragment of the group received
+    if constexpr (P::completions) {
       constexpr uint64_t gmask = (FP == 64) ? ~0ull : ((1ull << FP) - 1);
       const uint64_t ok = __ballot(valid && (fl >= t.Fe || got));
       const bool lead = fl == 0 && got && !t.collide && ((ok >> (lane & ~(FP - 1))) & gmask) == gmask;
-      if (lead) tr_count(t, u, GS_TR_RECEIVED);
+      if (lead) P::completed(t, u);
     }
     const uint64_t tt = key >> a.tshift;
     const uint32_t src = (uint32_t)(key & smask);
@@ -161,8 +200,8 @@ __global__ __launch_bounds__(TB) void k_traffic_fwd(RelaxArgs a, TrafficArgs t) 
     }
     const uint64_t start = uplink_start<FP>(nullptr, 0, got, key, n, ser, a.tshift);
     if (!n) continue;
-    PeerTraffic pt;
-    pt.send(n, t.W, t.pk, t.hdr);
+    typename P::Peer pt;
+    pt.data_tx(t, n);
     uint32_t pos = 0;
 #pragma unroll
     for (int j = 0; j < (int)MESH_W; j++) {
@@ -173,18 +212,20 @@ __global__ __launch_bounds__(TB) void k_traffic_fwd(RelaxArgs a, TrafficArgs t) 
       const uint32_t sd = a.tables[S * S + S + sw];
       const uint64_t arr = start + (uint64_t)pos * ser + a.tables[su * S + sw] + (sd > ser ? sd - ser : 0);
       if (a.churn && ev_lost(a, m, arr, w)) continue;
-      tr_arrive(t, w, t.W, t.pk, t.hdr);
-      pt.acked(1, t.pk);
+      P::data_arrive(t, w);
+      pt.data_acked(t, 1);
     }
     pt.flush(t, u);
   }
 }
+template <int FP>
+__global__ __launch_bounds__(TB) void k_traffic_fwd(RelaxArgs a, TrafficArgs t) { sends_fwd<TrafficAcc, FP>(a, t); }
 
 // Lazy gossip: every holder lane (the publisher's own
 // fragments from t_pub, a receiver's from its first receipt) at each of its
 // history_gossip heartbeats.
-template <int FP>
-__global__ __launch_bounds__(TB) void k_traffic_gossip(RelaxArgs a, TrafficArgs t) {
+template <class P, int FP>
+__device__ __forceinline__ void sends_gossip(const RelaxArgs& a, const typename P::Args& t) {
   const uint32_t S = a.S, LL = a.L;
   const uint64_t step = (uint64_t)gridDim.x * TB;
   for (uint64_t gid = (uint64_t)blockIdx.x * TB + threadIdx.x; gid < a.total; gid += step) {
@@ -196,7 +237,7 @@ __global__ __launch_bounds__(TB) void k_traffic_gossip(RelaxArgs a, TrafficArgs 
     const uint64_t ser = a.tables[S * S + sv];
     const uint64_t r0 = a.rel0[m];
     const uint64_t j0 = first_hb(tt, r0, a.hb_ns);
-    PeerTraffic pt;
+    typename P::Peer pt;
     for (uint32_t k = 0; k < a.hist; k++) {
       const uint64_t T = r0 + (j0 + k) * a.hb_ns;
       const uint64_t hab = a.habs0[m] + j0 + k;
@@ -206,20 +247,20 @@ __global__ __launch_bounds__(TB) void k_traffic_gossip(RelaxArgs a, TrafficArgs 
         const uint64_t ti = T + a.tables[sv * S + sw];
         const uint64_t sd = a.tables[S * S + S + sw];
         const uint64_t A = ti + a.tables[sw * S + sv] + ser + a.tables[sv * S + sw] + (sd > ser ? sd - ser : 0);
-        pt.send(1, t.ihw, t.ihpk, t.ihhd);  // IHAVE u -> w
+        pt.ihave_tx(t);  // IHAVE u -> w
         if (a.churn && ev_lost(a, m, ti, w)) return;
-        tr_arrive(t, w, t.ihw, t.ihpk, t.ihhd);
-        pt.acked(1, t.ihpk);
+        P::ihave_arrive(t, w);
+        pt.ihave_acked(t);
         const uint64_t kw = a.keys[(size_t)w * LL + slot];
         if (kw != INF64 && (kw >> a.tshift) <= ti) return;  // w has it: no IWANT
-        PeerTraffic wt;  // IWANT w -> u, then u's answer
-        wt.send(1, t.iww, t.iwpk, t.iwhd);
-        pt.recv(1, t.iww, t.iwpk, t.iwhd);
-        wt.acked(1, t.iwpk);
-        pt.send(1, t.W, t.pk, t.hdr);
+        typename P::Peer wt;  // IWANT w -> u, then u's answer
+        wt.iwant_tx(t);
+        pt.iwant_rx(t);
+        wt.iwant_acked(t);
+        pt.data_tx(t, 1);
         if (!(a.churn && ev_lost(a, m, A, w))) {
-          wt.recv(1, t.W, t.pk, t.hdr);
-          pt.acked(1, t.pk);
+          wt.data_rx(t);
+          pt.data_acked(t, 1);
         }
         wt.flush(t, w);
       });
@@ -227,3 +268,5 @@ __global__ __launch_bounds__(TB) void k_traffic_gossip(RelaxArgs a, TrafficArgs 
     pt.flush(t, u);
   }
 }
+template <int FP>
+__global__ __launch_bounds__(TB) void k_traffic_gossip(RelaxArgs a, TrafficArgs t) { sends_gossip<TrafficAcc, FP>(a, t); }

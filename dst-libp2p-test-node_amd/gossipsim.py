@@ -133,6 +133,10 @@ SIGNATURES = {
     "gs_write_node_metrics": (i32, [P(GsConfig), ctypes.c_char_p, P(u64), P(u8), P(u64)]),
     "gs_set_traffic": (i32, [ctypes.c_void_p, u32]),
     "gs_get_traffic": (i32, [ctypes.c_void_p, P(u64)]),
+    "gs_set_pubsub_counts": (i32, [ctypes.c_void_p, u32]),
+    "gs_get_pubsub_counts": (i32, [ctypes.c_void_p, P(u64)]),
+    "gs_reset_pubsub_counts": (i32, [ctypes.c_void_p]),
+    "gs_write_pubsub_metrics": (i32, [P(GsConfig), ctypes.c_char_p, u32, P(u64)]),
     "gs_set_peer_delay": (i32, [ctypes.c_void_p, u32]),
     "gs_get_peer_delay": (i32, [ctypes.c_void_p, P(GsPeerDelay)]),
     "gs_reset_peer_delay": (i32, [ctypes.c_void_p]),
@@ -267,6 +271,23 @@ def write_node_metrics(cfg, path, row_ptr, mesh_count, traffic):
     rc = lib().gs_write_node_metrics(ctypes.byref(cfg.c), path.encode(), _ptr(row, u64), _ptr(mc, u8), _ptr(tr, u64))
     if rc:
         raise GossipSimError(rc, "gs_write_node_metrics failed")
+
+
+# gs_get_pubsub_counts columns (GS_PS_*)
+PUBSUB_COLS = ("msg_tx", "msg_rx", "first", "dup", "ihave_tx", "ihave_rx", "iwant_tx", "iwant_rx")
+
+
+def write_pubsub_metrics(cfg, path, counts):
+    """Prometheus text of the go node's pubsub counters (libp2p_pubsub_*, libp2p_gossipsub_received /
+    duplicate, go-test-node/metrics.go:84-220) and the nim node's dst_testnode_received_chunks_total
+    for every peer (gs_write_pubsub_metrics). counts: uint64 [peers, len(PUBSUB_COLS)]
+    (Simulator.pubsub_counts)."""
+    pc = np.ascontiguousarray(counts, np.uint64)
+    if pc.ndim != 2 or pc.shape[1] != len(PUBSUB_COLS):
+        raise GossipSimError(GS_EINVAL, "counts [peers, %d] are needed" % len(PUBSUB_COLS))
+    rc = lib().gs_write_pubsub_metrics(ctypes.byref(cfg.c), path.encode(), pc.shape[0], _ptr(pc, u64))
+    if rc:
+        raise GossipSimError(rc, "gs_write_pubsub_metrics failed")
 
 
 def write_testnode_metrics(cfg, path, row_ptr, mesh_count, schedule, delay):
@@ -691,6 +712,26 @@ class Simulator:
     def write_node_metrics(self, path):
         """Every peer's Prometheus metrics (rust-test-node/src/metrics.rs names) after traffic runs."""
         write_node_metrics(self.cfg, path, self.csr()[0], self.mesh()[1], self.traffic())
+
+    # ---- per-peer pubsub event counts (gs_set_pubsub_counts, DESIGN.md §2.14) ----
+    def set_pubsub_counts(self, on=True):
+        """Per-peer event counters of later runs: fragment copies, IHAVEs and IWANTs sent and
+        received, first receipts and duplicates (zeroed now)."""
+        self._check(lib().gs_set_pubsub_counts(self.ctx, 1 if on else 0))
+
+    def pubsub_counts(self):
+        """-> uint64 [N, len(PUBSUB_COLS)] in PUBSUB_COLS order."""
+        pc = np.zeros((self.peers, len(PUBSUB_COLS)), np.uint64)
+        self._check(lib().gs_get_pubsub_counts(self.ctx, _ptr(pc, u64)))
+        return pc
+
+    def reset_pubsub_counts(self):
+        self._check(lib().gs_reset_pubsub_counts(self.ctx))
+
+    def write_pubsub_metrics(self, path):
+        """Every peer's go-node pubsub counters and the nim node's chunk counter after runs with
+        set_pubsub_counts."""
+        write_pubsub_metrics(self.cfg, path, self.pubsub_counts())
 
     # ---- what each node shows about delay (gs_set_peer_delay, DESIGN.md §2.13) ----
     def _own_rows(self):

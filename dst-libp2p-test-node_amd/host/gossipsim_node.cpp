@@ -26,11 +26,12 @@ void usage() {
           "         [--delay-ms MS] [--t0-s SECONDS] [--http-us US] [--max-heartbeats H] [--latencies PATH]\n"
           "         [--device-log]\n"
           "         [--gml network_topology.gml --yaml shadow.yaml] [--schedule FILE] [--shadowlog PATH] [--metrics PATH]\n"
-          "         [--testnode-metrics PATH]\n"
+          "         [--testnode-metrics PATH] [--pubsub-metrics PATH]\n"
           "  --yaml also supplies the injector's -s/-m/-d and start_time unless given on the command line\n"
           "  --device-log writes --latencies from the device-formatted text (gs_run_log), one fwrite per chunk\n"
           "  --testnode-metrics writes the nim node's per-peer delay metrics (dst_testnode_*, gs_set_peer_delay);\n"
           "    a run with a latency of 65535 ms or more then fails\n"
+          "  --pubsub-metrics writes the go node's per-peer pubsub counters (libp2p_pubsub_*, gs_set_pubsub_counts)\n"
           "env: PEERS CONNECTTO FRAGMENTS MUXER MAXCONNECTIONS GOSSIPSUB_* SELFTRIGGER GS_NODE GS_SEED GS_BATCH\n"
           "     GS_DEVICE\n");
 }
@@ -117,7 +118,7 @@ int main(int argc, char** argv) {
   // the POST reaches the node 1.5 round trips over the 1 ms injector-hub links
   // after the injector sends it (topogen.py:64-69); tx_time is stamped then
   uint64_t http_us = 3000;
-  std::string latencies, gml, yaml, shadowlog, metrics, schedule, testnode;
+  std::string latencies, gml, yaml, shadowlog, metrics, schedule, testnode, pubsub;
   bool set_size = false, set_msgs = false, set_delay = false, set_t0 = false, device_log = false;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -146,6 +147,7 @@ int main(int argc, char** argv) {
     else if (a == "--shadowlog") shadowlog = next(); // tracker counters for summary_shadowlog.awk
     else if (a == "--metrics") metrics = next();    // the node metrics (rust-test-node/src/metrics.rs)
     else if (a == "--testnode-metrics") testnode = next();  // the nim node's metrics (gossipsub-queues/main.nim:25-78)
+    else if (a == "--pubsub-metrics") pubsub = next();  // the go node's pubsub counters (go-test-node/metrics.go:84-220)
     else if (a == "--schedule") schedule = next();  // rows: t_pub_ns publisher msg_size [frags]
     else { usage(); return 2; }
   }
@@ -188,6 +190,7 @@ int main(int argc, char** argv) {
   const bool counters = !shadowlog.empty() || !metrics.empty();
   if (counters && (st = gs_set_traffic(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_traffic");
   if (!testnode.empty() && (st = gs_set_peer_delay(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_peer_delay");
+  if (!pubsub.empty() && (st = gs_set_pubsub_counts(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_pubsub_counts");
   if ((st = gs_build_topology(ctx)) != GS_OK) return die(ctx, st, "gs_build_topology");
   uint32_t epochs = 0;
   if ((st = gs_mesh_converge(ctx, max_hb, &epochs)) != GS_OK) return die(ctx, st, "gs_mesh_converge");
@@ -249,7 +252,7 @@ int main(int argc, char** argv) {
     strm.hist_ms.clear();
     if (!latencies.empty() && (st = gs_log_open(&cfg, latencies.c_str(), &strm.log)) != GS_OK)
       return die(ctx, st, "gs_log_open");
-    gs_reset_stats(ctx);  // (also restarts the per-peer traffic counters)
+    gs_reset_stats(ctx);  // (also restarts the per-peer traffic and pubsub counters)
     gs_result_sink wide{};
     wide.want = GS_WANT_T_COMPLETE;
     wide.on_block = on_block;
@@ -303,6 +306,12 @@ int main(int argc, char** argv) {
     if ((st = gs_write_testnode_metrics(&cfg, testnode.c_str(), row.data(), mc.data(), sched.data(), n_msgs,
                                         pd.data())) != GS_OK)
       return die(ctx, st, "gs_write_testnode_metrics");
+  }
+  if (!pubsub.empty()) {
+    std::vector<uint64_t> pc((size_t)cfg.peers * GS_PUBSUB_COLS);
+    if ((st = gs_get_pubsub_counts(ctx, pc.data())) != GS_OK) return die(ctx, st, "gs_get_pubsub_counts");
+    if ((st = gs_write_pubsub_metrics(&cfg, pubsub.c_str(), cfg.peers, pc.data())) != GS_OK)
+      return die(ctx, st, "gs_write_pubsub_metrics");
   }
   gs_destroy(ctx);
   return 0;

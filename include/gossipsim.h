@@ -478,6 +478,46 @@ gs_status gs_set_traffic(struct gs_ctx* ctx, uint32_t enable);
 /* Copy the per-peer counters out: traffic[peers][GS_TRAFFIC_COLS]. */
 gs_status gs_get_traffic(struct gs_ctx* ctx, uint64_t* traffic);
 
+/* ---- per-peer pubsub event counts --------------------------
+ * What go-test-node/metrics.go:84-220 counts per node, and the nim node's
+ * dst_testnode_received_chunks_total (main.nim:37-41). The events are exactly
+ * the sends, arrivals and losses gs_set_traffic accounts;
+ * here each is counted, not weighed in bytes. A "message" is one fragment copy. */
+enum { GS_PS_MSG_TX = 0,    /* fragment copies sent: flood-publish, forwards (after IDONTWANT  */
+                            /* skips), IWANT answers; sends lost to churn included             */
+       GS_PS_MSG_RX = 1,    /* copies that arrived (a lost send is not counted, as for rx traffic) */
+       GS_PS_FIRST = 2,     /* first receipts of a fragment at a non-publisher                 */
+       GS_PS_DUP = 3,       /* duplicates: MSG_RX - FIRST                                      */
+       GS_PS_IHAVE_TX = 4, GS_PS_IHAVE_RX = 5,  /* IHAVE RPCs sent / arrived                   */
+       GS_PS_IWANT_TX = 6, GS_PS_IWANT_RX = 7,  /* IWANT RPCs sent / arrived                   */
+       GS_PUBSUB_COLS = 8 };
+/* 1: every batch of gs_run and gs_run_log adds its events to per-peer counters
+ * on the device (extra passes over the final keys, as gs_set_traffic: off by
+ * default, diagnostic). Enabling allocates and zeroes the counters; they carry
+ * across batches and calls and are zeroed by gs_reset_pubsub_counts and
+ * gs_reset_stats. IDONTWANT, GRAFT, PRUNE and subscription RPCs are not
+ * counted. Partitioned mode (gs_part_begin, gs_run_partitioned*) returns
+ * GS_EUNSUPPORTED while the switch is on. gs_save_state does not carry the
+ * counters: a loaded context has the switch off. */
+gs_status gs_set_pubsub_counts(struct gs_ctx* ctx, uint32_t enable);
+/* out[peers][GS_PUBSUB_COLS]. GS_ESTATE while the switch is off. */
+gs_status gs_get_pubsub_counts(struct gs_ctx* ctx, uint64_t* out);
+gs_status gs_reset_pubsub_counts(struct gs_ctx* ctx);
+
+/* The go node's pubsub counters (go-test-node/metrics.go:84-220, help strings
+ * verbatim) and the nim node's chunk counter for every peer, in the Prometheus
+ * text exposition format ("# HELP" / "# TYPE" per family), one series per peer
+ * labelled peer_id="pod-<id>", with topic="test" first where metrics.go has a
+ * topic label: libp2p_pubsub_broadcast_messages_total (MSG_TX),
+ * libp2p_pubsub_received_messages_total (MSG_RX),
+ * libp2p_pubsub_broadcast_ihave_total, libp2p_pubsub_received_ihave_total,
+ * libp2p_pubsub_broadcast_iwant_total, libp2p_pubsub_received_iwant_total,
+ * libp2p_gossipsub_received_total (FIRST), libp2p_gossipsub_duplicate_total
+ * (DUP) and dst_testnode_received_chunks_total (FIRST; labels muxer, peer_id as
+ * main.nim:40). counts[peers][GS_PUBSUB_COLS] is a host copy
+ * (gs_get_pubsub_counts). Host only. */
+gs_status gs_write_pubsub_metrics(const gs_config* cfg, const char* path, uint32_t peers, const uint64_t* counts);
+
 /* ---- what each node shows about delay ---------------------
  * The per-peer application metrics of nim-test-node/gossipsub-queues
  * (main.nim:25-78,147-154), reduced on the device from the logged latencies
@@ -536,8 +576,9 @@ gs_status gs_peer_delay_add_lat(struct gs_ctx*, const gs_publish* sched, uint64_
  * dst_testnode_message_delay_ms_sum, the histogram dst_testnode_message_delay_ms
  * (cumulative _bucket{le=...}, _sum, _count), dst_testnode_last_message_delay_ms,
  * dst_testnode_mesh_size (mesh_count) and dst_testnode_topic_peers (CSR degree).
- * dst_testnode_received_chunks_total is not written: it counts fragment first
- * arrivals, which completion does not keep per peer. Arrays are host copies:
+ * dst_testnode_received_chunks_total is not written here: it counts fragment
+ * first arrivals, which completion does not keep per peer
+ * (gs_write_pubsub_metrics writes it from the event counters). Arrays are host copies:
  * row_ptr[peers+1], mesh_count[peers], delay[peers] (gs_get_peer_delay; the
  * parts' arrays side by side). Host only. */
 gs_status gs_write_testnode_metrics(const gs_config* cfg, const char* path, const uint64_t* row_ptr,
@@ -639,7 +680,8 @@ gs_status gs_comm_destroy(gs_comm* comm);
  * the batch's messages for all peers, one all-to-all hands every part its own
  * peers' rows; gs_stats.ms_batches counts them). Collective over the
  * communicator. Results are bit-identical to gs_run. GS_EUNSUPPORTED: per-peer
- * traffic (gs_set_traffic), and sink summaries of a message-sharded batch.
+ * traffic (gs_set_traffic), per-peer pubsub counts (gs_set_pubsub_counts), and
+ * sink summaries of a message-sharded batch.
  * Every sinks[i] follows gs_result_sink's rules (GS_EINVAL otherwise); on_lat
  * receives [n][own peers] u16, and the parts' blocks side by side are gs_run's
  * on_lat stream. GS_ERANGE (a logged latency of 65535 ms or more): no part, and

@@ -17,6 +17,7 @@ pub const GS_ABI_VERSION: u32 = 10;
 pub const GS_NODE_RUST: u32 = 0;
 pub const GS_TRAFFIC_COLS: usize = 12; // GS_TR_*: tx/rx bytes, packets, header bytes, received,
                                        // published, tx/rx ACK packets, tx/rx ACK header bytes
+pub const GS_PUBSUB_COLS: usize = 8; // GS_PS_*: msg tx/rx, first, dup, ihave tx/rx, iwant tx/rx
 pub const GS_HIST_BINS: usize = 64;
 pub const GS_DELAY_BUCKETS: usize = 12; // le = 1 .. 10000 ms (nim gossipsub-queues main.nim:59)
 pub const GS_CTRL_IHAVE: u32 = 0;
@@ -143,6 +144,11 @@ extern "C" {
     pub fn gs_set_timing(ctx: *mut gs_ctx, enable: u32) -> gs_status;
     pub fn gs_set_traffic(ctx: *mut gs_ctx, enable: u32) -> gs_status;
     pub fn gs_get_traffic(ctx: *mut gs_ctx, traffic: *mut u64) -> gs_status;
+    pub fn gs_set_pubsub_counts(ctx: *mut gs_ctx, enable: u32) -> gs_status;
+    pub fn gs_get_pubsub_counts(ctx: *mut gs_ctx, out: *mut u64) -> gs_status;
+    pub fn gs_reset_pubsub_counts(ctx: *mut gs_ctx) -> gs_status;
+    pub fn gs_write_pubsub_metrics(cfg: *const gs_config, path: *const c_char, peers: u32, counts: *const u64)
+                                   -> gs_status;
     pub fn gs_set_peer_delay(ctx: *mut gs_ctx, enable: u32) -> gs_status;
     pub fn gs_get_peer_delay(ctx: *mut gs_ctx, out: *mut gs_peer_delay) -> gs_status;
     pub fn gs_reset_peer_delay(ctx: *mut gs_ctx) -> gs_status;
