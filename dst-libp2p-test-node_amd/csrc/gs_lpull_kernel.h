@@ -761,27 +761,65 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
   if constexpr (STREAM && !CHN) {
     if (w < a.N) swh = a.stage[u0 + w];
   }
+  // EARLY (single-fragment rows of 1024 lanes on the frozen mesh; rows of 512 run at
+  // 80 VGPRs with pointers in scratch, whose reloads on the way to the first record
+  // loads are vmcnt(0) waits themselves: nothing to gain there): the row loop's header waits
+  // for nothing. Every load that feeds a row's header values (ej, rj, sv, swh, dw,
+  // and cj / ro, gathered through ej) is awaited, or is older than a load that is
+  // awaited with a counted wait, before the row's first store; at the back edge
+  // only stores are pending. A wait at the header would be a vmcnt(0) (the stores
+  // of the append and emit loops cannot be counted): the previous row's store
+  // acknowledgements and then an uncovered round trip for the next row's header
+  // loads issued just before it. The empty asm is a use: the compiler places the
+  // wait for its operands there.
+  constexpr bool EARLY = STREAM && !CHN && CH == 16;
+  // the loads of a header's lists: cj and, younger, PART's ro
+  auto await_lists = [](uint32_t c, uint64_t r) {
+    if constexpr (PART) asm volatile("" ::"v"(c), "v"(r));
+    else asm volatile("" ::"v"(c));
+  };
+  if constexpr (EARLY) {
+    await_lists(cj, ro);
+    asm volatile("" ::"v"(sv), "v"(swh));
+    if constexpr (GOS) asm volatile("" ::"v"(dw));
+  }
   for (; w < a.N; w = wn) {
     PP_T(tA);
     wn = am ? base + (uint32_t)__builtin_ctzll(am) * stride : a.N;  // the next active row
     am &= am - 1;
     const uint32_t w2 = wn;
     uint32_t ej2 = EMPTY, rj2 = 0, cj2 = 0, sv2 = 0, dw2 = 0;
-    if constexpr (CHN) {
-      if (w2 < a.N) {
-        ej2 = a.ccol[(size_t)w2 * CELL_W + lane];
-        rj2 = a.cpos[(size_t)w2 * CELL_W + lane];
-        if (lane < (int)LP_SW) sv2 = a.st[(size_t)w2 * LP_SW + lane];
-      }
-    } else if (w2 < a.N && lane < (int)MESH_W) {  // w2 < N is wave-uniform
-      ej2 = a.mesh[(size_t)(u0 + w2) * MESH_W + lane];
-      rj2 = a.rpos[(size_t)(u0 + w2) * MESH_W + lane];
-      sv2 = a.st[(size_t)w2 * LP_SW + lane];
-    }
-    if (GOS && gw && w2 < a.N) dw2 = a.rowdone[w2 >> 5];
     uint32_t swh2 = 0;
-    if constexpr (STREAM && !CHN) {
+    // EARLY: the next row's header is loaded on either side of the idle-row test
+    // below, not in front of it. The compiler joins the two sides in one block
+    // ahead of the latch, and a load issued in front of the test counts as
+    // pending on the path that skips both: the copies at the latch then wait
+    // for it with a vmcnt(0), the drain that the header no longer has.
+    auto next_header = [&]() {
+      if (w2 < a.N && lane < (int)MESH_W) {  // w2 < N is wave-uniform
+        ej2 = a.mesh[(size_t)(u0 + w2) * MESH_W + lane];
+        rj2 = a.rpos[(size_t)(u0 + w2) * MESH_W + lane];
+        sv2 = a.st[(size_t)w2 * LP_SW + lane];
+      }
+      if (GOS && gw && w2 < a.N) dw2 = a.rowdone[w2 >> 5];
       if (w2 < a.N) swh2 = a.stage[u0 + w2];
+    };
+    if constexpr (!EARLY) {
+      if constexpr (CHN) {
+        if (w2 < a.N) {
+          ej2 = a.ccol[(size_t)w2 * CELL_W + lane];
+          rj2 = a.cpos[(size_t)w2 * CELL_W + lane];
+          if (lane < (int)LP_SW) sv2 = a.st[(size_t)w2 * LP_SW + lane];
+        }
+      } else if (w2 < a.N && lane < (int)MESH_W) {  // w2 < N is wave-uniform
+        ej2 = a.mesh[(size_t)(u0 + w2) * MESH_W + lane];
+        rj2 = a.rpos[(size_t)(u0 + w2) * MESH_W + lane];
+        sv2 = a.st[(size_t)w2 * LP_SW + lane];
+      }
+      if (GOS && gw && w2 < a.N) dw2 = a.rowdone[w2 >> 5];
+      if constexpr (STREAM && !CHN) {
+        if (w2 < a.N) swh2 = a.stage[u0 + w2];
+      }
     }
     const uint64_t cand = __ballot(cj != 0);
     const uint32_t pr = pk_get();  // this row's copy of the packed scalars
@@ -805,6 +843,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
     if (cand == 0 && due == 0 && !gossip_row) {  // nothing to apply, nothing due: the pending windows stay
       if (lane == 0) wcnt_of(pr)[w] = 0;
       if (lane < (int)pk_f(pr, PK_K, 4) && sv) nmh = umin32(nmh, lwhi);
+      if constexpr (EARLY) next_header();
       if (pullr && lane < (int)HW && ej2 != EMPTY) {
         cj2 = rcnt[ej2 & 0xFFFFFFu];
         if constexpr (PART) ro2 = a.roff[ej2 & 0xFFFFFFu];
@@ -812,11 +851,13 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
           if (!((runi[ej2 & 0xFFFFFFu] >> (rj2 & 63u)) & 1)) cj2 = 0;
         }
       }
+      if constexpr (EARLY) await_lists(cj2, ro2);  // (the next row's header loads are older)
       ej = ej2; rj = rj2; cj = cj2; sv = sv2; ro = ro2; dw = dw2; swh = swh2;
       PP_T(tS);
       PP_ADD(0, tS - tA);
       continue;
     }
+    if constexpr (EARLY) next_header();
     PP_ADD(7, 1);
     const uint32_t sw = STREAM && !CHN ? swh : a.stage[u0 + w];
     // final bits transposed: lane j holds bit q for lane q*64 + j (u16 per lane)
@@ -1020,6 +1061,15 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
           for (int k = 0; k < (int)NG; k++) issue(k);
           ent = false;  // the listed entries and the table values while the first records are in flight
           apply_entries(e);
+          // EARLY: the next row's lists now (its header, loaded at the top of this
+          // row, is older than the entries just awaited), in front of the stream's
+          // refills: every turn's counted wait makes them older than an awaited load
+          if constexpr (EARLY) {
+            if (lane < (int)HW && ej2 != EMPTY) {
+              cj2 = rcnt[ej2 & 0xFFFFFFu];
+              if constexpr (PART) ro2 = a.roff[ej2 & 0xFFFFFFu];
+            }
+          }
           sds = __builtin_amdgcn_readfirstlane(sd);
 #pragma unroll
           for (int k = 0; k < (int)NG; k++) take_key(k, J[k]);
@@ -1039,6 +1089,7 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
               more |= REM[k] > 0;
             }
           } while (more);  // (what is in flight now is past every neighbour's records)
+          if constexpr (EARLY) await_lists(cj2, ro2);  // older than the last turn's loads: a counted wait
         }
       }
       while (!STREAM && cmk) {
@@ -1130,7 +1181,18 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
     for (int off = 32; off > 0; off >>= 1) cb |= __shfl_xor(cb, off);
     cb = __builtin_amdgcn_readfirstlane(cb);
     wave_lds_sync();
-    if (pullr && lane < (int)HW && ej2 != EMPTY) {  // next row's lists
+    // next row's lists
+    if constexpr (EARLY) {
+      // (a row with candidates gathered them in the record step; one without: here, and awaited
+      // in the same block, before the row's stores)
+      if (cand == 0) {
+        if (pullr && lane < (int)HW && ej2 != EMPTY) {
+          cj2 = rcnt[ej2 & 0xFFFFFFu];
+          if constexpr (PART) ro2 = a.roff[ej2 & 0xFFFFFFu];
+        }
+        await_lists(cj2, ro2);
+      }
+    } else if (pullr && lane < (int)HW && ej2 != EMPTY) {
       cj2 = rcnt[ej2 & 0xFFFFFFu];
       if constexpr (PART) ro2 = a.roff[ej2 & 0xFFFFFFu];
       if constexpr (CHN) {
@@ -1255,111 +1317,21 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
       const uint32_t serw = lat[Se * Se + sw];  // sup[sw]
       uint64_t* const wrec = wrec_of(pe);
       constexpr uint32_t GPW = 64 / FP;
-      for (uint32_t g0 = 0; g0 < cnt; g0 += GPW) {
-        const uint32_t gi = g0 + (uint32_t)lane / FP;
-        const bool gv = gi < cnt;
-        const uint32_t grp = gv ? LST[gi] : 0;
-        const uint32_t i = grp * FP + (lane & (FP - 1));
-        const uint64_t x = gv ? CW[i] : INF64;  // final lanes were set to INF in step 3
-        // the message's publisher (excluded from the receivers); a row that is
-        // no publisher nor a publisher's neighbour needs none (no load)
-        uint32_t pm = EMPTY;
-        if (needp) pm = gv ? a.pub[psl + grp] : EMPTY;
-        // FP == 1: LST holds only lanes final in window c; a fragment group's
-        // other lanes are re-checked
-        const bool act = gv && (FP == 1 || (x != INF64 && ((uint32_t)(x >> 32) - hlo) < hspan)) && u0 + w != pm;
-        const uint32_t src = (uint32_t)x & ((1u << sbe) - 1u);  // sb < 32
-        uint32_t xm = 0;  // excluded mesh indices: source, publisher (IDW: and IDONTWANT)
-        uint64_t im64 = 0;  // churn: the receivers as a mask over the CSR row
-        if constexpr (CHN) {  // the mesh of the epoch the lane was received in, less source and publisher
-          const uint32_t kk = kc + ((x >> tse) >= eBc ? 1u : 0u);
-          const uint64_t mmv = act ? a.cmm[(size_t)w * a.cE + a.cq[grp] + kk] : 0ull;
-          uint64_t xm64 = 0;
-          for (uint32_t k = 0; k < deg; k++) {  // wave-uniform: entry k from lane k
-            const uint32_t y = __builtin_amdgcn_readlane(ej, k) & 0xFFFFFFu;
-            xm64 |= (y == src || y == pm) ? 1ull << k : 0ull;
-          }
-          im64 = mmv & ~xm64;
-        } else if constexpr (IDW) {
-          // IDONTWANT from y already here: ky + lat(y -> w) <= t_w. The keys of
-          // IB mesh entries are loaded before any is tested (one round trip per
-          // IB entries instead of one per entry; CH = 8 rows run at 80 VGPRs).
-          // Fragment groups: lane i is one fragment, so a group's lanes read
-          // consecutive keys of y's row (one segment per group); a lane not
-          // final in this window (act false: final earlier, pending or
-          // padding) loads nothing and counts no receiver
-          constexpr uint32_t IB = CH == 8 ? 2 : 8;
-          const uint64_t tw = x >> tse;
-          for (uint32_t k0 = 0; k0 < deg; k0 += IB) {  // wave-uniform: entry k from lane k
-            uint64_t ky[IB];
-#pragma unroll
-            for (uint32_t u = 0; u < IB; u++) {
-              const uint32_t k = k0 + u;
-              const uint32_t y = k < deg ? (uint32_t)__builtin_amdgcn_readlane(ej, k) & 0xFFFFFFu : src;
-              ky[u] = act && y != src && y != pm ? a.keys[(size_t)y * LL + i] : INF64;
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < IB; u++) {
-              const uint32_t k = k0 + u;
-              if (k >= deg) break;  // (wave-uniform)
-              const uint32_t e = __builtin_amdgcn_readlane(ej, k);
-              const uint32_t y = e & 0xFFFFFFu;
-              const bool sk = y == src || y == pm ||
-                              (ky[u] != INF64 && (ky[u] >> tse) + lat[(e >> STAGE_SHIFT) * Se + sw] <= tw);
-              xm |= sk ? 1u << k : 0u;
-            }
-          }
+      // one loop body with the publisher and, where the publisher load is the
+      // loop's only load, one without it for the rows that need none
+      // (gs_lpull_emit.h); fragment groups (busy), IDONTWANT (keys) and churn
+      // (cmm) load in the loop anyway and keep the single body
+      if constexpr (FP == 1 && !IDW && !CHN) {
+        if (needp) {
+#define LP_EMIT_PUB 1
+#include "gs_lpull_emit.h"
         } else {
-          for (uint32_t k = 0; k < deg; k++) {  // wave-uniform: entry k from lane k
-            const uint32_t y = __builtin_amdgcn_readlane(ej, k) & 0xFFFFFFu;
-            xm |= (y == src || y == pm) ? 1u << k : 0u;
-          }
+#define LP_EMIT_PUB 0
+#include "gs_lpull_emit.h"
         }
-        const uint32_t im = CHN ? 0u : ((1u << deg) - 1u) & ~xm;  // the receivers (deg <= MESH_W = 16)
-        const uint32_t n = act ? (CHN ? (uint32_t)__popcll(im64) : (uint32_t)__popc(im)) : 0u;
-        const uint64_t start = uplink_start<FP>(a.busy, (size_t)w * a.B + grp, act, x, n, serw, tse);
-        const uint32_t hp = (uint32_t)(x >> sbe) & hmask;
-        if (act) {
-          fd++;
-          nr += n;
-          if constexpr (NOLOG) {  // k_lsum's ms: floor(t / 1e6) = floor(floor(t / 64) / 15625), t < 2^38
-            s_ls += (uint32_t)((x >> tse) >> 6) / 15625u;
-            s_max = x > s_max ? x : s_max;  // the key orders by time first
-          }
-          if (n && hp + 1 >= (1u << HOP_BITS)) err |= ERR_HOPS;
-          if (start - wlo >= (1ull << 32) || (n && start >= tlim)) err |= ERR_TIME;
-        }
-        // act as lane masks: listed (gi < cnt) and not the message's publisher
-        const uint64_t fm = FP == 1 ? (__builtin_amdgcn_uicmp(gi, cnt, 36) & __builtin_amdgcn_uicmp(pm, u0 + w, 33))
-                                    : __ballot(act);  // final log: 64 entries per store
-        if constexpr (IDW) {
-          if (act) a.keys[(size_t)w * LL + i] = x;  // dense: the neighbours' IDONTWANT tests read it
-        } else if constexpr (!NOLOG) {
-          if (act) {
-            const uint32_t p =
-                logc + __builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
-            // the final log is read after the passes (completion): stream it past the caches
-            __builtin_nontemporal_store(x, &a.keys[(size_t)w * LL + p]);
-            __builtin_nontemporal_store((uint16_t)i, &a.flane[(size_t)w * LL + p]);
-          }
-          logc += (uint32_t)__popcll(fm);
-        }
-        const bool want = act && n != 0;
-        const uint64_t wm = fm & __builtin_amdgcn_uicmp(n, 0u, 33);
-        if (want) {
-          const size_t ri = (size_t)w * LL + ecnt +
-                            __builtin_amdgcn_mbcnt_hi((uint32_t)(wm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wm, 0u));
-          if constexpr (CHN) {
-            uni |= im64;
-            const uint64_t r0 = ((start - wlo) << 32) | ((uint64_t)hp << LP_HOP_SHIFT) | i;
-            *reinterpret_cast<uint4*>(wrec + ri * 2) =
-                make_uint4((uint32_t)r0, (uint32_t)(r0 >> 32), (uint32_t)im64, (uint32_t)(im64 >> 32));
-          } else {
-            const uint64_t rv = ((start - wlo) << 32) | ((uint64_t)hp << LP_HOP_SHIFT) | ((uint64_t)im << LP_IM_SHIFT) | i;
-            wrec[ri] = rv;
-          }
-        }
-        ecnt += (uint32_t)__popcll(wm);
+      } else {
+#define LP_EMIT_PUB 1
+#include "gs_lpull_emit.h"
       }
     }
     PP_T(tD);
