@@ -170,7 +170,6 @@ struct Ctx {
   // dissemination (per batch)
   DevBuf<uint64_t> d_keys;   // [N * B * FP] peer-major (u, m, f)
   DevBuf<uint64_t> d_busy;   // [N * B] uplink FIFO end per (u, m) (F > 1)
-  DevBuf<uint64_t> d_meta;   // per-64-lane tile metadata (TileMeta, 16 B)
   DevBuf<uint64_t> d_fbits;  // final bitset, one u64 per 64-lane tile
   DevBuf<uint32_t> d_fr_idx; // bucket frontier (per-scan-wave segments)
   DevBuf<uint64_t> d_fr_key;

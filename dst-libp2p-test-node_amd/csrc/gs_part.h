@@ -768,7 +768,7 @@ bool part_lp_begin(Ctx& c, const gs_publish* sched, uint64_t n_msgs) {
   const uint32_t F = part_check(c, sched, n_msgs);
   (void)F;
   // without bit 64 (or with GS_PART_PUSH) the push protocol runs
-  if (!(env_int("GS_RELAX_VARIANT", 64) & 64) || getenv("GS_PART_PUSH")) return false;
+  if (!path_knob().list || getenv("GS_PART_PUSH")) return false;
   hipStream_t s = c.stream;
   GS_HIP(hipMemsetAsync(c.d_counters.p + C_ERR, 0, 8, s));
   ensure_cus(c);

@@ -1,50 +1,51 @@
 // gs_relax_kernel.h — the hot kernels: one Delta-bucket of eager forwarding.
 // Included by gs_relax.hip only (inside namespace gs::{anon}).
 //
-// Two implementations of one bucket, selected by GS_RELAX_VARIANT (bit 8):
+// Two implementations of one bucket (PushForm, gs_run.h):
 //
-//  * fused  k_relax: a wave owns 64 consecutive key lanes ("a tile"); it
-//    scans them and forwards its active lanes in place. With 64 messages per
-//    batch and F = 1 a tile is one peer's row, so pushes into a target w hit
-//    one 512-B row. Only ~1/5 of the lanes are active per bucket and every
-//    tile is a dependent chain (key -> mesh row -> final bits -> atomics), so
-//    the kernel is latency bound.
-//  * split  k_scan + k_frontier (default): the scan streams the keys,
+//  * split  k_scan + k_frontier (the default): the scan streams the keys,
 //    compacts the bucket's arrivals with a wave ballot + mbcnt prefix into a
 //    per-wave frontier segment (no returning atomics), and stores the final
 //    bitset; the frontier kernel then runs the forward chain with every lane
 //    carrying a real arrival (items of one peer stay adjacent, so pushes stay
-//    row-coalesced).
+//    row-coalesced). Frontier indices are 32-bit, so it needs fewer than 2^32
+//    key lanes.
+//  * fused  k_relax (batches of 2^32 key lanes or more, or GS_RELAX_VARIANT
+//    without bit 8): a wave owns 64 consecutive key lanes ("a tile"); it scans
+//    them and forwards its active lanes in place. With 64 messages per batch
+//    and F = 1 a tile is one peer's row, so pushes into a target w hit one
+//    512-B row. Only ~1/5 of the lanes are active per bucket and every tile is
+//    a dependent chain (key -> mesh row -> final bits -> atomics), so the
+//    kernel is latency bound.
 //
-// Option bits (all exact):
-//   1 FILTER  read the target key first, atomicMin only when smaller
-//   2 SKIP    per-tile {min pending key, scan stamp, push stamp} (fused); split:
-//             per-tile min pending key + touched flag (+ next IHAVE arrival,
-//             non-final count and scan stamp with lazy gossip)
-//   4 FB      final bitset, 1 bit per key (N*L/8 bytes, L2/MALL resident),
-//             written by the scanner; a push to a final target is dropped (a
-//             final key cannot improve: every push lands >= the bucket end)
-//   8 SPLIT   scan + frontier instead of the fused kernel
+// Both read the target key first and atomicMin only when the new key is
+// smaller, and both keep the final bitset: 1 bit per key (N*L/8 bytes, L2/MALL
+// resident), written by the scanner; a push to a final target is dropped (a
+// final key cannot improve: every push lands >= the bucket end).
+//
+// One option, chosen by the code (PushForm::skip): with lazy gossip or churn
+// the split path keeps per-tile state, the min pending key + a touched flag
+// (+ the next IHAVE arrival, non-final count and scan stamp with lazy gossip),
+// and its scan visits only the tiles that can hold work in the bucket.
 
-struct TileMeta {
-  uint64_t tmin;     // min pending key (>= that launch's bucket end) at last scan
-  uint32_t scanned;  // stamp (launch + 1) of the last scan
-  uint32_t pushed;   // stamp of the last atomic push into the tile
+// The form a batch's buckets run in (Run::push_form, gs_run.h). skip implies
+// split, and a batch with lazy gossip always runs with both.
+struct PushForm {
+  bool split, skip;
 };
 
 struct RelaxArgs {
   uint64_t* keys;
   uint64_t* busy;
-  TileMeta* meta;
   uint64_t* fbits;
   uint32_t* fr_idx;   // frontier: group index (gid / FP), per-wave segments
   uint64_t* fr_key;   // frontier: key (FP == 1)
   uint32_t* fr_cnt;   // frontier: items per wave segment
-  uint64_t* tmin;     // split SKIP: min pending key per tile at its last scan
-  uint8_t* touched;   // split SKIP: tile received a push since its last scan
-  uint64_t* tgmin;    // split SKIP + gossip: next IHAVE arrival time of the tile's lanes (INF none)
-  uint32_t* tnf;      // split SKIP + gossip: non-final lanes of the tile at its last scan
-  uint32_t* tstamp;   // split SKIP + gossip: launch + 1 of the tile's last scan (k_gossip's seen filter)
+  uint64_t* tmin;     // tile skip: min pending key per tile at its last scan
+  uint8_t* touched;   // tile skip: tile received a push since its last scan
+  uint64_t* tgmin;    // tile skip + gossip: next IHAVE arrival time of the tile's lanes (INF none)
+  uint32_t* tnf;      // tile skip + gossip: non-final lanes of the tile at its last scan
+  uint32_t* tstamp;   // tile skip + gossip: launch + 1 of the tile's last scan (k_gossip's seen filter)
   // lazy gossip
   uint32_t* gl_idx;   // gossip list: lane gid with an IHAVE arrival in this bucket
   uint32_t* gl_cnt;   // per scan wave
@@ -302,7 +303,7 @@ __device__ __forceinline__ uint64_t uplink_start(uint64_t* busy, size_t bi, bool
 // Forward one lane's first arrival (key at lane gid = u*L + slot). `active`
 // must be true only for lanes finalised in this bucket; every lane of the wave
 // must call this (FP > 1 shuffles across the FP-aligned lane group).
-template <int FP, bool FILTER, bool SKIP, bool FB, bool TOUCH = false>
+template <int FP, bool TOUCH>
 __device__ __forceinline__ void relax_lane(const RelaxArgs& a, const BucketLds& L, bool active,
                                            uint64_t key, uint32_t u, uint32_t slot, uint32_t pm,
                                            uint64_t& nmin, uint64_t& fd, uint64_t& nr, uint64_t& np, uint32_t& err) {
@@ -349,21 +350,17 @@ __device__ __forceinline__ void relax_lane(const RelaxArgs& a, const BucketLds& 
   if (n && hp + 1 >= (1u << HOP_BITS)) err |= ERR_HOPS;
   const uint64_t hbits = ((uint64_t)(hp + 1) << a.sb) | u;
   uint32_t fin = 0;  // targets already final: they still take an uplink slot
-  if constexpr (FB) {
-    uint64_t fw[MESH_W];
+  uint64_t fw[MESH_W];
 #pragma unroll
-    for (int j = 0; j < (int)MESH_W; j++)
-      fw[j] = (skip & (1u << j)) ? 0 : a.fbits[((size_t)(row[j] & 0xFFFFFFu) * LL + slot) >> 6];
+  for (int j = 0; j < (int)MESH_W; j++)
+    fw[j] = (skip & (1u << j)) ? 0 : a.fbits[((size_t)(row[j] & 0xFFFFFFu) * LL + slot) >> 6];
 #pragma unroll
-    for (int j = 0; j < (int)MESH_W; j++)
-      if ((fw[j] >> ((((size_t)(row[j] & 0xFFFFFFu)) * LL + slot) & 63)) & 1) fin |= 1u << j;
-  }
-  uint64_t old[MESH_W];
-  if constexpr (FILTER) {
+  for (int j = 0; j < (int)MESH_W; j++)
+    if ((fw[j] >> ((((size_t)(row[j] & 0xFFFFFFu)) * LL + slot) & 63)) & 1) fin |= 1u << j;
+  uint64_t old[MESH_W];  // read filter: atomicMin only when the new key is smaller
 #pragma unroll
-    for (int j = 0; j < (int)MESH_W; j++)
-      old[j] = ((skip | fin) & (1u << j)) ? 0 : a.keys[(size_t)(row[j] & 0xFFFFFFu) * LL + slot];
-  }
+  for (int j = 0; j < (int)MESH_W; j++)
+    old[j] = ((skip | fin) & (1u << j)) ? 0 : a.keys[(size_t)(row[j] & 0xFFFFFFu) * LL + slot];
   uint32_t pos = 0;
 #pragma unroll
   for (int j = 0; j < (int)MESH_W; j++) {
@@ -377,11 +374,10 @@ __device__ __forceinline__ void relax_lane(const RelaxArgs& a, const BucketLds& 
     if (arr > a.tmax) err |= ERR_TIME;
     if (a.churn && ev_lost(a, slot / FP, arr, w)) continue;  // the send still took its uplink slot
     const uint64_t nk = (arr << a.tshift) | hbits;
-    if (FILTER && !(nk < old[j])) continue;
+    if (!(nk < old[j])) continue;
     const size_t dst = (size_t)w * LL + slot;
     atomicMin((unsigned long long*)&a.keys[dst], (unsigned long long)nk);
     np++;
-    if constexpr (SKIP) a.meta[dst >> 6].pushed = a.launch + 1;
     if constexpr (TOUCH) a.touched[dst >> 6] = 1;
     nmin = nk < nmin ? nk : nmin;
   }
@@ -404,7 +400,7 @@ __device__ __forceinline__ void flush_wave(const RelaxArgs& a, uint64_t nmin, ui
 }
 
 // ---------------------------------------------------------------- fused ----
-template <int FP, bool FILTER, bool SKIP, bool FB>
+template <int FP>
 __global__ __launch_bounds__(TB) void k_relax(RelaxArgs a) {
   __shared__ BucketLds L;
   if (blockIdx.x == 0 && threadIdx.x == 0) a.ctrl[(a.launch + 2) % 3] = INF64;
@@ -414,7 +410,7 @@ __global__ __launch_bounds__(TB) void k_relax(RelaxArgs a) {
   __syncthreads();
   if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd((unsigned long long*)&a.counters[C_BUCKETS], 1ull);
   const uint64_t lo = ((cur >> a.tshift) / a.delta) * a.delta, hi = lo + a.delta;
-  const uint32_t LL = a.L, stamp = a.launch + 1;
+  const uint32_t LL = a.L;
   const int lane = threadIdx.x & 63;
   uint64_t nmin = INF64, fd = 0, nr = 0, np = 0;
   uint32_t err = 0;
@@ -422,16 +418,6 @@ __global__ __launch_bounds__(TB) void k_relax(RelaxArgs a) {
   const uint64_t nwaves = (uint64_t)gridDim.x * (TB / 64);
   for (uint64_t tile = uniform64((uint64_t)blockIdx.x * (TB / 64) + (threadIdx.x >> 6)); tile < ntiles;
        tile += nwaves) {
-    if constexpr (SKIP) {
-      const TileMeta tm = a.meta[tile];
-      const uint64_t tmin = uniform64(tm.tmin);
-      const uint32_t scanned = __builtin_amdgcn_readfirstlane(tm.scanned);
-      const uint32_t pushed = __builtin_amdgcn_readfirstlane(tm.pushed);
-      if (pushed < scanned && (tmin == INF64 || (tmin >> a.tshift) >= hi)) {
-        nmin = tmin < nmin ? tmin : nmin;
-        continue;
-      }
-    }
     const uint64_t gid = (tile << 6) + lane;
     const bool valid = gid < a.total;
     const uint64_t key = valid ? a.keys[gid] : INF64;
@@ -443,18 +429,9 @@ __global__ __launch_bounds__(TB) void k_relax(RelaxArgs a) {
     const bool active = pending && t >= lo && t < hi && u != pm;
     const uint64_t later = (pending && t >= hi) ? key : INF64;
     nmin = later < nmin ? later : nmin;
-    if constexpr (FB) {
-      const uint64_t fw = __ballot(pending && t < hi);
-      if (lane == 0) a.fbits[tile] = fw;
-    }
-    relax_lane<FP, FILTER, SKIP, FB>(a, L, active, key, u, slot, pm, nmin, fd, nr, np, err);
-    if constexpr (SKIP) {
-      const uint64_t tm = wave_min(later);
-      if (lane == 0) {
-        a.meta[tile].tmin = tm;
-        a.meta[tile].scanned = stamp;
-      }
-    }
+    const uint64_t fw = __ballot(pending && t < hi);
+    if (lane == 0) a.fbits[tile] = fw;
+    relax_lane<FP, false>(a, L, active, key, u, slot, pm, nmin, fd, nr, np, err);
   }
   flush_wave(a, nmin, fd, nr, np, err);
 }
@@ -1036,7 +1013,7 @@ __global__ __launch_bounds__(TB) void k_gossip(RelaxArgs a) {
 }
 
 // Frontier: every lane carries one compacted arrival (FP lanes per group).
-template <int FP, bool FILTER, bool TOUCH>
+template <int FP, bool TOUCH>
 __global__ __launch_bounds__(TB) void k_frontier(RelaxArgs a) {
   __shared__ BucketLds L;
   const uint64_t cur = a.ctrl[a.launch % 3];
@@ -1068,48 +1045,35 @@ __global__ __launch_bounds__(TB) void k_frontier(RelaxArgs a) {
     const uint32_t slot = (uint32_t)(gid - (uint64_t)u * LL);
     const uint32_t pm = valid ? a.pub[slot / FP] : EMPTY;
     const bool active = valid && key != INF64 && t >= lo && t < hi && u != pm;
-    relax_lane<FP, FILTER, false, true, TOUCH>(a, L, active, key, u, slot, pm, nmin, fd, nr, np, err);
+    relax_lane<FP, TOUCH>(a, L, active, key, u, slot, pm, nmin, fd, nr, np, err);
   }
   flush_wave(a, nmin, fd, nr, np, err);
 }
 
 // ------------------------------------------------------------- dispatch ----
+// One bucket in form f. mid (timing): recorded between scan and frontier.
 template <int FP>
-void relax_fp(uint32_t variant, const RelaxArgs& a, unsigned grid, hipStream_t s, hipEvent_t mid) {
-  if (variant & 8) {
-    if (a.gossip && (variant & 2)) k_scan<FP, true, true><<<grid, TB, 0, s>>>(a);
-    else if (a.gossip) k_scan<FP, false, true><<<grid, TB, 0, s>>>(a);
-    else if (variant & 2) k_scan<FP, true, false><<<grid, TB, 0, s>>>(a);
-    else k_scan<FP, false, false><<<grid, TB, 0, s>>>(a);
-    if (mid) (void)hipEventRecord(mid, s);  // splits scan / frontier time when timing
-    switch (variant & 3) {
-      case 0: k_frontier<FP, false, false><<<grid, TB, 0, s>>>(a); break;
-      case 1: k_frontier<FP, true, false><<<grid, TB, 0, s>>>(a); break;
-      case 2: k_frontier<FP, false, true><<<grid, TB, 0, s>>>(a); break;
-      default: k_frontier<FP, true, true><<<grid, TB, 0, s>>>(a); break;
-    }
-    if (a.gossip) k_gossip<FP><<<grid, TB, 0, s>>>(a);
+void relax_fp(PushForm f, const RelaxArgs& a, unsigned grid, hipStream_t s, hipEvent_t mid) {
+  if (!f.split) {
+    k_relax<FP><<<grid, TB, 0, s>>>(a);
     return;
   }
-  switch (variant & 7) {
-    case 0: k_relax<FP, false, false, false><<<grid, TB, 0, s>>>(a); break;
-    case 1: k_relax<FP, true, false, false><<<grid, TB, 0, s>>>(a); break;
-    case 2: k_relax<FP, false, true, false><<<grid, TB, 0, s>>>(a); break;
-    case 3: k_relax<FP, true, true, false><<<grid, TB, 0, s>>>(a); break;
-    case 4: k_relax<FP, false, false, true><<<grid, TB, 0, s>>>(a); break;
-    case 5: k_relax<FP, true, false, true><<<grid, TB, 0, s>>>(a); break;
-    case 6: k_relax<FP, false, true, true><<<grid, TB, 0, s>>>(a); break;
-    default: k_relax<FP, true, true, true><<<grid, TB, 0, s>>>(a); break;
-  }
+  if (!f.skip) k_scan<FP, false, false><<<grid, TB, 0, s>>>(a);
+  else if (a.gossip) k_scan<FP, true, true><<<grid, TB, 0, s>>>(a);
+  else k_scan<FP, true, false><<<grid, TB, 0, s>>>(a);
+  if (mid) (void)hipEventRecord(mid, s);  // splits scan / frontier time when timing
+  if (f.skip) k_frontier<FP, true><<<grid, TB, 0, s>>>(a);
+  else k_frontier<FP, false><<<grid, TB, 0, s>>>(a);
+  if (a.gossip) k_gossip<FP><<<grid, TB, 0, s>>>(a);
 }
 
-void relax_dispatch(uint32_t FP, uint32_t variant, const RelaxArgs& a, unsigned grid, hipStream_t s,
+void relax_dispatch(uint32_t FP, PushForm f, const RelaxArgs& a, unsigned grid, hipStream_t s,
                     hipEvent_t mid = nullptr) {
   switch (FP) {
-    case 1: relax_fp<1>(variant, a, grid, s, mid); break;
-    case 2: relax_fp<2>(variant, a, grid, s, mid); break;
-    case 4: relax_fp<4>(variant, a, grid, s, mid); break;
-    case 8: relax_fp<8>(variant, a, grid, s, mid); break;
-    default: relax_fp<16>(variant, a, grid, s, mid); break;
+    case 1: relax_fp<1>(f, a, grid, s, mid); break;
+    case 2: relax_fp<2>(f, a, grid, s, mid); break;
+    case 4: relax_fp<4>(f, a, grid, s, mid); break;
+    case 8: relax_fp<8>(f, a, grid, s, mid); break;
+    default: relax_fp<16>(f, a, grid, s, mid); break;
   }
 }

@@ -132,20 +132,37 @@ static void glp_account(Ctx& c, uint64_t iwant0, uint32_t n) {
   else if ((c.glp_quiet += n) >= GLP_QUIET) c.glp_prefer = false;
 }
 
-// ---- one batch on the push path ----
+// GS_RELAX_VARIANT: the paths a run may take, a bit mask (default 237, every path
+// on): owner-computes pull (32) over candidate lists (64), fragmented batches too
+// (128; config #2 7.2e8 against 6.7e8/s on k_pull's dense rows, round 4); k_pull's
+// dense rows without 64; without 32 the push path, split into scan + frontier (8).
+// Bits 1, 2 and 4 selected forms of the push path that are gone and are not read.
+struct PathKnob {
+  bool pull, list, frag_list, split;
+};
+static PathKnob path_knob() {
+  const long e = env_int("GS_RELAX_VARIANT", -1), v = e < 0 ? 237 : e;  // unset or negative: the default
+  return {(v & 32) != 0, (v & 64) != 0, (v & 128) != 0, (v & 8) != 0};
+}
 
-// Fresh keys and bucket state for variant v (the list pull path needs no dense keys).
-static void reset_batch(Ctx& c, const Batch& b, uint32_t v, bool with_gossip, bool dense_keys, size_t max_tiles) {
+// Fresh keys and uplink FIFO state for a batch on any path (the list pull path
+// needs no dense keys).
+static void reset_keys(Ctx& c, const Batch& b, bool dense_keys) {
   hipStream_t s = c.stream;
   const uint32_t N = c.cfg.peers;
-  const uint64_t total = (uint64_t)N * b.L;
   c.keys_log = c.keys_none = false;
-  if (dense_keys) GS_HIP(hipMemsetAsync(c.d_keys.p, 0xFF, total * 8, s));
+  if (dense_keys) GS_HIP(hipMemsetAsync(c.d_keys.p, 0xFF, (uint64_t)N * b.L * 8, s));
   if (b.FP > 1) GS_HIP(hipMemsetAsync(c.d_busy.p, 0, (size_t)N * b.B * 8, s));
-  if (v & 32) return;
-  if (v & 2) GS_HIP(hipMemsetAsync(c.d_meta.p, 0, (total + 63) / 64 * sizeof(TileMeta), s));
-  if (v & 12) GS_HIP(hipMemsetAsync(c.d_fbits.p, 0, (total + 63) / 64 * 8, s));
-  if ((v & 10) == 10) {  // split + tile skip: tmin 0 forces every tile's first scan
+}
+
+// ---- one batch on the push path ----
+
+// Fresh bucket state for the push path in form f.
+static void reset_push(Ctx& c, const Batch& b, PushForm f, bool with_gossip, size_t max_tiles) {
+  hipStream_t s = c.stream;
+  const uint64_t total = (uint64_t)c.cfg.peers * b.L;
+  GS_HIP(hipMemsetAsync(c.d_fbits.p, 0, (total + 63) / 64 * 8, s));
+  if (f.skip) {  // tmin 0 forces every tile's first scan
     c.d_tmin.alloc(max_tiles);
     c.d_touched.alloc(max_tiles);
     GS_HIP(hipMemsetAsync(c.d_tmin.p, 0, (total + 63) / 64 * 8, s));
@@ -165,13 +182,13 @@ static void reset_batch(Ctx& c, const Batch& b, uint32_t v, bool with_gossip, bo
 
 // The split path's frontier segments (one per scan wave) and, with gossip, its
 // gossip and holder lists.
-static void push_lists(Ctx& c, const Batch& b, uint32_t v, bool with_gossip, unsigned grid, RelaxArgs& ra) {
+static void push_lists(Ctx& c, const Batch& b, PushForm f, bool with_gossip, unsigned grid, RelaxArgs& ra) {
   hipStream_t s = c.stream;
   const uint32_t FP = b.FP;
   const uint64_t total = (uint64_t)c.cfg.peers * b.L;
   const uint64_t nwaves = (uint64_t)grid * (TB / 64), ntiles = (total + 63) / 64;
   // tiles one scan wave can visit: groups of 64 with tile skip (k_scan), single tiles without
-  const uint64_t gt = (v & 2) ? 64 : 1;
+  const uint64_t gt = f.skip ? 64 : 1;
   const uint64_t wave_tiles = ((ntiles + gt - 1) / gt + nwaves - 1) / nwaves * gt;
   ra.seg_cap = (uint32_t)(wave_tiles * (64 / FP));
   c.d_fr_idx.alloc(nwaves * ra.seg_cap);
@@ -215,21 +232,22 @@ static void push_lists(Ctx& c, const Batch& b, uint32_t v, bool with_gossip, uns
     ra.hl_end = c.d_hl_mark.p + HL_LAUNCHES;
   }
   ra.nonfinal = c.d_nonfinal.p;
-  if ((v & 10) == 10) {
+  if (f.skip) {
     ra.tgmin = c.d_tgmin.p;
     ra.tnf = c.d_tnf.p;
     ra.tstamp = c.d_tstamp.p;
   }
 }
 
-// One batch on the push path, variant v: k_seed, then bucket launches in chunks of
+// One batch on the push path in form f: k_seed, then bucket launches in chunks of
 // 8 until the ctrl word of the next bucket is empty. g0 (churn + lazy gossip): the
 // earliest time an IHAVE of the batch can arrive.
-static void run_push_batch(Ctx& c, const Batch& b, uint32_t v, bool with_gossip, uint64_t g0, size_t max_tiles) {
+static void run_push_batch(Ctx& c, const Batch& b, PushForm f, bool with_gossip, uint64_t g0, size_t max_tiles) {
   hipStream_t s = c.stream;
   const uint32_t N = c.cfg.peers, FP = b.FP;
   const uint64_t total = (uint64_t)N * b.L;
-  reset_batch(c, b, v, with_gossip, true, max_tiles);
+  reset_keys(c, b, true);
+  reset_push(c, b, f, with_gossip, max_tiles);
   launch_seed(c, b, 0, N);
   RelaxArgs ra = relax_args(c, b, with_gossip);
   if (ra.ring_in) {
@@ -237,7 +255,6 @@ static void run_push_batch(Ctx& c, const Batch& b, uint32_t v, bool with_gossip,
     ra.g0 = g0;
   }
   ra.busy = c.d_busy.p;
-  ra.meta = reinterpret_cast<TileMeta*>(c.d_meta.p);
   ra.fbits = c.d_fbits.p;
   ra.tmin = c.d_tmin.p;
   ra.touched = c.d_touched.p;
@@ -245,7 +262,7 @@ static void run_push_batch(Ctx& c, const Batch& b, uint32_t v, bool with_gossip,
   ra.counters = c.d_counters.p; ra.delta = b.delta;
   const uint64_t need = (total + TB - 1) / TB;
   const unsigned grid = (unsigned)std::min<uint64_t>(need, (uint64_t)c.num_cus * SPLIT_BLOCKS_PER_CU);
-  if (v & 8) push_lists(c, b, v, with_gossip, grid, ra);
+  if (f.split) push_lists(c, b, f, with_gossip, grid, ra);
   uint32_t launch = 0;
   const uint32_t chunk = 8;
   for (;;) {
@@ -256,15 +273,12 @@ static void run_push_batch(Ctx& c, const Batch& b, uint32_t v, bool with_gossip,
       if (c.timing) {  // (start, scan end, end) per bucket
         GS_HIP(hipEventRecord(run_ev(c, c.ev_n), s));
         const hipEvent_t mid = run_ev(c, c.ev_n + 1);
-        if (v & 8) relax_dispatch(FP, v, ra, grid, s, mid);
-        else {
-          relax_dispatch(FP, v, ra, grid, s);
-          GS_HIP(hipEventRecord(mid, s));
-        }
+        relax_dispatch(FP, f, ra, grid, s, mid);
+        if (!f.split) GS_HIP(hipEventRecord(mid, s));  // the fused kernel: all of it counts as scan
         GS_HIP(hipEventRecord(run_ev(c, c.ev_n + 2), s));
         c.ev_n += 3;
       } else {
-        relax_dispatch(FP, v, ra, grid, s);
+        relax_dispatch(FP, f, ra, grid, s);
       }
     }
     GS_HIP(hipGetLastError());
@@ -531,7 +545,7 @@ struct Run {
   const bool pipe_on;
   PassStream pass_stream;
   const bool gossip, churn;
-  uint32_t variant = 0, pvariant = 0;
+  const PathKnob knob;
   bool lanes32 = false, pull_any = false, chn_any = false;
   size_t max_tiles = 0;
   uint32_t sl_max = 0;      // GS_SLICES
@@ -546,32 +560,22 @@ struct Run {
   Run(Ctx& cc, const gs_publish* sched_, uint64_t n, const gs_result_sink* sink_, const std::vector<uint8_t>* cut_)
       : c(cc), sched(sched_), n_msgs(n), sink(sink_), cut(cut_), N(cc.cfg.peers), Bmax(cc.cfg.batch),
         sw(sink_wants(cc, sink_)), async_off(cc), pipe_on(chain_pipe_wanted(cc)), pass_stream(cc, pipe_on),
-        gossip(cc.cfg.lazy_gossip != 0), churn(cc.cfg.churn_ppm != 0), q0v(Bmax), r0v(Bmax), rel0(Bmax),
-        habs0(Bmax), q0a(Bmax), r0a(Bmax), malive(Bmax), ah(cc) {
+        gossip(cc.cfg.lazy_gossip != 0), churn(cc.cfg.churn_ppm != 0), knob(path_knob()), q0v(Bmax), r0v(Bmax),
+        rel0(Bmax), habs0(Bmax), q0a(Bmax), r0a(Bmax), malive(Bmax), ah(cc) {
     hipStream_t s = c.stream;
     GS_HIP(hipMemsetAsync(c.d_counters.p + C_ERR, 0, 8, s));
     check_schedule(c, sched, n_msgs);
     uint32_t Fmax = 1;
     for (uint64_t i = 0; i < n_msgs; i++) Fmax = std::max(Fmax, frags_of(c, sched[i]));
     const uint32_t FPmax = pow2_at_least(Fmax);
-    const long var_env = env_int("GS_RELAX_VARIANT", -1);  // a bit mask; unset (< 0): the default below
-    // default: owner-computes pull over candidate lists (64 | 32), fragmented batches
-    // too (128; config #2 7.2e8 against 6.7e8/s on k_pull's dense rows, round 4);
-    // k_pull's dense rows without 64; without 32 the push path: split (8) + final
-    // bitset (4) + read filter (1)
-    variant = var_env < 0 ? 237u : (uint32_t)var_env;
-    lanes32 = (uint64_t)N * Bmax * FPmax < (1ull << 32);  // frontier indices are u32
-    if (!lanes32) variant &= ~8u;
+    lanes32 = (uint64_t)N * Bmax * FPmax < (1ull << 32);  // frontier and gossip list indices are u32
     // the pull path needs rows in LDS and one mesh per batch (churn uses one per
     // epoch: the push path, or the churn list pass)
-    pull_any = (variant & 32) && !churn;
+    pull_any = knob.pull && !churn;
     // churn on the list pass (gs_cpull.h): CSR rows of <= 64 entries (<= 58 with lazy gossip:
     // the IHAVE entry's target mask); GS_CHURN_LIST=0 keeps churn batches on the push path
-    chn_any = churn && (variant & 32) && (variant & 64) && !env_off("GS_CHURN_LIST") &&
+    chn_any = churn && knob.pull && knob.list && !env_off("GS_CHURN_LIST") &&
               c.max_degree <= (gossip ? GSE_HOPS : CELL_W) && N < (1u << 21);
-    // the push path with gossip or churn runs split + tile skip (its long tail of
-    // IHAVE and churn buckets touches few tiles); GS_RELAX_VARIANT can turn the skip off
-    pvariant = (gossip || churn) ? (((variant | 8u) & ~32u) | (var_env < 0 ? 2u : 0u)) : (variant & ~32u);
     if (churn && !lanes32) c.fail(GS_EUNSUPPORTED, "churn needs peers*batch*FP < 2^32");
     if (churn) {  // epoch of every publish; the snapshot ring
       for (uint64_t i = 0; i < n_msgs; i++)
@@ -581,7 +585,6 @@ struct Run {
     }
     max_tiles = ((size_t)N * Bmax * FPmax + 63) / 64;
     c.d_keys.alloc((size_t)N * Bmax * FPmax);
-    c.d_meta.alloc(max_tiles * sizeof(TileMeta) / 8);
     c.d_fbits.alloc(max_tiles);
     if (FPmax > 1) c.d_busy.alloc((size_t)N * Bmax);
     c.d_tc.alloc((size_t)N * Bmax);
@@ -631,7 +634,17 @@ struct Run {
 
   // The list pass can take batches of FP lanes per message at all: bit 64; rows of
   // fragment groups with bit 128 (the default).
-  bool list_pass_any(uint32_t FP) const { return (variant & 64) && (FP == 1 || (variant & 128)); }
+  bool list_pass_any(uint32_t FP) const { return knob.list && (FP == 1 || knob.frag_list); }
+
+  // The push path's form for a batch; gc: it runs with lazy gossip or churn. Those
+  // run split + tile skip (their long tail of IHAVE and churn buckets touches few
+  // tiles; gossip and churn exist on the split path only: run_batch and the
+  // constructor refuse what its 32-bit indices cannot hold). Else split wherever its
+  // indices fit, unless the knob asks for the fused kernel.
+  PushForm push_form(bool gc) const {
+    const bool split = gc || (lanes32 && knob.split);
+    return {split, split && gc};
+  }
 
   // The plan of batch b but for its churn list pass (chn_admit). rel: rel0 of its n messages
   // (lazy gossip); sliced: a slice group's pass (frozen mesh, no per-peer traffic, never no-log).
@@ -648,8 +661,8 @@ struct Run {
     // them on the push path (A/B, per batch). With colliding fragments (defect D8)
     // only lane 0 of a group is ever final, as without IDONTWANT. k_pull has no
     // IDONTWANT: such a batch needs the list pass (bit 64).
-    const bool idw_frag = (variant & 128) && !env_off("GS_IDW_FRAG_LIST");
-    p.pull = pull_any && p.win >= pull_grain(b.tshift) && (!p.idw || ((variant & 64) && (b.FP == 1 || idw_frag)));
+    const bool idw_frag = knob.frag_list && !env_off("GS_IDW_FRAG_LIST");
+    p.pull = pull_any && p.win >= pull_grain(b.tshift) && (!p.idw || (knob.list && (b.FP == 1 || idw_frag)));
     p.lp = p.pull && list_pass_any(b.FP);
     p.glp = p.lp && gossip && gossip_list_admit(c, b, p);
     p.dense = dense_rows(c, sw, p.idw);
@@ -928,7 +941,7 @@ struct Run {
       if (gossip && !lanes32)
         c.fail(GS_EUNSUPPORTED, "lazy gossip changes this batch and the push path needs "
                                 "peers*batch*FP < 2^32: use a smaller batch");
-      run_push_batch(c, r.b, pvariant, gossip, r.g0, max_tiles);
+      run_push_batch(c, r.b, push_form(gossip || churn), gossip, r.g0, max_tiles);
       complete(r);
     }
     c.stats.messages += B;
@@ -1036,7 +1049,7 @@ struct Run {
     const uint64_t grain = pull_grain(b.tshift);
     const uint32_t K = lpull_ring(c, bc, bc.delta / grain * grain, &lb, gossip, true);
     if (K) {
-      reset_batch(c, b, variant, false, false, max_tiles);
+      reset_keys(c, b, false);
       const GosRun gr{rel0[0], c.cfg.heartbeat_ns};
       const ChnRun cr{h_lo, r0v[0], (uint32_t)(h_end - h_lo + 1), gossip ? (uint32_t)(habs0[0] - q0v[0]) : 0u, r.cp.par};
       // the next batch's chain beside these passes, from the first pass group on:
@@ -1093,7 +1106,7 @@ struct Run {
     uint32_t lb = 0;
     const uint32_t K = lpull_ring(c, bg, bg.delta / grain * grain, &lb, true);
     if (!K) return false;
-    reset_batch(c, b, variant, false, r.p.idw, max_tiles);  // IDONTWANT: dense INF keys (the finals stay dense rows)
+    reset_keys(c, b, r.p.idw);  // IDONTWANT: dense INF keys (the finals stay dense rows)
     const GosRun gr{rel0[0], c.cfg.heartbeat_ns};
     const uint64_t iw0 = read_counter(c, C_GOSSIP);
     LpOpts o = r.p.opts();
@@ -1110,12 +1123,12 @@ struct Run {
   void run_eager(BatchRun& r) {
     const Batch& b = r.b;
     const PathPlan& p = r.p;
-    if (!p.pull) return run_push_batch(c, b, variant & ~32u, false, r.g0, max_tiles);
+    if (!p.pull) return run_push_batch(c, b, push_form(false), false, r.g0, max_tiles);
     const uint64_t grain = pull_grain(b.tshift);
     uint32_t lb = 0;
     const Batch bw = with_window(b, p.win);
     const uint32_t K = p.lp ? lpull_ring(c, bw, bw.delta / grain * grain, &lb) : 0u;
-    reset_batch(c, b, variant, false, K == 0 || p.idw, max_tiles);  // IDONTWANT: dense INF keys
+    reset_keys(c, b, K == 0 || p.idw);  // IDONTWANT: dense INF keys
     if (p.lp && !K && getenv("GS_REQUIRE_LPULL"))  // test knob: no silent k_pull fallback
       c.fail(GS_EUNSUPPORTED, "list pull path cannot take this batch (GS_REQUIRE_LPULL)");
     r.nl.on = K && p.nolog;
@@ -1130,9 +1143,9 @@ struct Run {
     r.nl.on = false;
     if (K && getenv("GS_REQUIRE_LPULL")) c.fail(GS_EUNSUPPORTED, "list pull overflow (GS_REQUIRE_LPULL)");
     if (p.idw) {  // k_pull has no IDONTWANT: the push path takes the batch
-      run_push_batch(c, b, variant & ~32u, false, r.g0, max_tiles);
+      run_push_batch(c, b, push_form(false), false, r.g0, max_tiles);
     } else {  // a candidate list overflowed (or no ring fits): this batch runs on k_pull
-      if (K) reset_batch(c, b, variant, false, true, max_tiles);
+      if (K) reset_keys(c, b, true);
       run_pull_batch(c, b);
     }
   }

@@ -392,11 +392,17 @@ def test_large_graph_properties_and_sampled_parity():
         np.testing.assert_array_equal(res["hops"][m], hp[0])
 
 
-@pytest.mark.parametrize("variant", list(range(8)) + [8, 9, 10, 11, 13, 15, 45, 109, 237])
+@pytest.mark.parametrize("variant", [0, 8, 45, 109, 237])
 def test_relax_kernel_variants_exact(variant, monkeypatch):
-    """Every bucket implementation (fused with read-filter / tile-skip / final-bitset,
-    split scan+frontier, owner-computes pull over dense rows = 45, over candidate
-    lists = 109, the default, and 237 = lists for fragmented batches too) is bit-exact."""
+    """Every form GS_RELAX_VARIANT selects is bit-exact, on a fragmented (FP = 2)
+    and a single-fragment batch shape:
+      0    the push path's fused kernel (k_relax<2>, k_relax<1>)
+      8    the push path split: k_scan<., false, false> + k_frontier<., false>
+      45   owner-computes pull over dense rows (k_pull)
+      109  pull over candidate lists (k_lpull) for F = 1, k_pull for F = 2
+      237  the default: candidate lists for fragmented batches too
+    (The split path's tile skip is chosen by the code, with lazy gossip or churn:
+    the gossip and churn tests on the push path reach it.)"""
     monkeypatch.setenv("GS_RELAX_VARIANT", str(variant))
     if variant & 64:
         monkeypatch.setenv("GS_REQUIRE_LPULL", "1")
