@@ -74,7 +74,33 @@
               xm |= sk ? 1u << k : 0u;
             }
           }
+        } else if constexpr (XMV) {
+          // rows of 1024 single-fragment lanes (XMV, set by the includer with ejm,
+          // the entries' peer ids): entry k from lane k by constant lane index, a
+          // block for entries 15-8 in the rows that have them (wave-uniform) and
+          // one for 7-0, not a loop of deg trips (a lane read by a scalar index,
+          // its shift and mask, the counter and the branch were 10 instructions
+          // per entry). The lanes past deg hold EMPTY's low 24 bits, no peer's id
+          // (no src) and not EMPTY (no pm), and im keeps only the bits below deg.
+          auto xblock = [&](const int k0) {
+#pragma unroll
+            for (int k = k0 + 7; k >= k0; k--) {
+              const uint32_t y = __builtin_amdgcn_readlane(ejm, k);
+              // (from the top entry down, the mask doubled and the compare added:
+              // the compiler reads each lane once and needs no shift per bit)
+#if LP_EMIT_PUB
+              xm = xm + xm + (uint32_t)(y == src || y == pm);
+#else
+              xm = xm + xm + (uint32_t)(y == src);
+#endif
+            }
+          };
+          static_assert(MESH_W == 16, "the excluded-entry mask: two blocks of 8 mesh entries");
+          if (deg > 8) xblock(8);
+          xblock(0);
         } else {
+          // (rows of 512 lanes and fragment groups sit at their VGPR limits: the
+          // unrolled form costs every one of them scratch)
           for (uint32_t k = 0; k < deg; k++) {  // wave-uniform: entry k from lane k
             const uint32_t y = __builtin_amdgcn_readlane(ej, k) & 0xFFFFFFu;
 #if LP_EMIT_PUB

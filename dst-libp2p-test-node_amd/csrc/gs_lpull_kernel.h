@@ -1208,9 +1208,46 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
     PP_ADD(2, tR - tG);
     const uint32_t log0 = NOLOG ? 0u : __builtin_amdgcn_readlane(sv, LP_LOG);
     uint32_t logc = log0, cnt = 0, npend = 0, nfin = 0;  // the finals are logged in step 4
+    // Single-fragment rows of 1024 lanes: the step is bound by the instructions it
+    // issues, not by LDS latency. The minima of eight
+    // chunks are read ahead of their use (the record step's registers are free
+    // here; an unmarked chunk reads INF and its work is skipped), and a chunk's
+    // three compares are taken as lane masks only: the masks select a lane's
+    // position (finals from the front, pendings from the back, both ascending by
+    // lane as below) for one LST store under am | pm, and set the final bits.
+    constexpr bool CLS8 = FP == 1 && CH == 16;
+    if constexpr (CLS8) {
+#pragma unroll
+      for (int h = 0; h < (int)CH; h += 8) {
+        if (!((cb >> h) & 0xFFu)) continue;  // wave-uniform
+        uint64_t xs[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) xs[u] = CW[(h + u) * 64 + lane];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+          const int q = h + u;
+          if (!((cb >> q) & 1u)) continue;  // wave-uniform
+          const uint64_t x = xs[u];
+          const uint64_t dead = __builtin_amdgcn_uicmp(finT & (1u << q), 0u, 33) | __builtin_amdgcn_uicmpl(x, INF64, 32);
+          const uint64_t bw = __builtin_amdgcn_uicmp((uint32_t)(x >> 32) - hlo, hspan, 36);
+          const uint64_t am = bw & ~dead, pm = ~(bw | dead);
+          const uint32_t fpos = cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
+          const uint32_t ppos = LMAX - 1 - npend -
+                                __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
+          // (a wave-uniform mask as the lanes' own bits: no second compare)
+          const bool act = __builtin_amdgcn_inverse_ballot_w64(am);
+          if (__builtin_amdgcn_inverse_ballot_w64(am | pm)) LST[act ? fpos : ppos] = (uint16_t)(q * 64 + lane);
+          finT |= act ? 1u << q : 0u;
+          cnt += (uint32_t)__popcll(am);
+          npend += (uint32_t)__popcll(pm);
+        }
+      }
+      nfin = cnt != 0;
+    }
+    // the other forms (rows of 512 lanes, fragment groups): chunk by chunk, nothing if CLS8
 #pragma unroll
     for (int q = 0; q < (int)CH; q++) {
-      if (!((cb >> q) & 1u)) continue;  // wave-uniform
+      if (CLS8 || !((cb >> q) & 1u)) continue;  // wave-uniform
       const uint32_t i = q * 64 + lane;
       const uint64_t x = CW[i];
       const bool fe = (finT & (1u << q)) != 0;  // final in an earlier window: dropped
@@ -1317,6 +1354,17 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
       const uint32_t serw = lat[Se * Se + sw];  // sup[sw]
       uint64_t* const wrec = wrec_of(pe);
       constexpr uint32_t GPW = 64 / FP;
+      // rows of 1024 single-fragment lanes: the row's mesh peers without their stage
+      // bits, once per row, for the emit step's excluded-entry mask, which reads
+      // them by constant lane index (the empty asm keeps the mask from moving
+      // behind each of the lane reads). The other forms keep the loop over the
+      // row's entries: they have no VGPR to spare
+      constexpr bool XMV = FP == 1 && CH == 16 && !IDW && !CHN;
+      [[maybe_unused]] uint32_t ejm = ej;
+      if constexpr (XMV) {
+        ejm &= 0xFFFFFFu;
+        asm volatile("" : "+v"(ejm));
+      }
       // one loop body with the publisher and, where the publisher load is the
       // loop's only load, one without it for the rows that need none
       // (gs_lpull_emit.h); fragment groups (busy), IDONTWANT (keys) and churn
