@@ -6,6 +6,7 @@
 
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gossipsim.h"
@@ -25,6 +26,20 @@ struct Error {
   std::string msg;
   Error(gs_status c, std::string m) : code(c), msg(std::move(m)) {}
 };
+
+// One dispatch on a batch's lanes per message: f(std::integral_constant<int, FP>{}) for
+// FP in {1, 2, 4, 8, 16}. FP = pow2_at_least(F) with F <= MAX_FRAGS, so the throw cannot fire.
+template <class Fn>
+void with_fp(uint32_t FP, Fn&& f) {
+  switch (FP) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+  }
+  throw Error(GS_EINVAL, "internal: " + std::to_string(FP) + " lanes per message (not 1, 2, 4, 8 or 16)");
+}
 
 // Environment knobs (DESIGN.md §6.1 lists every one the library reads). Both
 // call getenv every time: tests set os.environ between runs of one process. A
@@ -80,6 +95,34 @@ enum : uint32_t {
                                                        // lanes, tiles scanned, of them only for gossip
   C_COUNT = 16
 };
+
+// The pull and list passes' control, Ctx::d_pctrl (gs_pull_kernel.h): PS_SLOTS slots of
+// {lo, mode, records emitted, min pending key}. Pass k writes slot k % 3 and decides from
+// slot (k + 2) % 3; k_seed leaves the seeds' min key in the slot pass 0 decides from.
+enum : uint64_t { PM_DONE = 0, PM_EMIT = 1, PM_PULL = 2 };
+enum : uint32_t {
+  PS_LO = 0, PS_MODE = 1, PS_RECORDS = 2, PS_MIN = 3, PS_WORDS = 4, PS_SLOTS = 3,
+  PS_SEED_MIN = (PS_SLOTS - 1) * PS_WORDS + PS_MIN
+};
+
+// Ctx::h_pinned, the pinned host mirror. Words [0, HP_SCRATCH) are any call's read-back,
+// valid from its copy to its next use of the mirror and no longer (collect_stats: C_COUNT
+// words; part_lp_route_read: LP_PMAX; PRun::check_same_config: 16; the passes' PS_SLOTS
+// slots). The words above are written by one function and read by another later on:
+enum : uint32_t {
+  HP_SCRATCH = 16,
+  HP_GATHER = 16,    // [HP_GATHER_WORDS] PRun::gather's own row on its way to the device (gs_prun.h)
+  HP_LP_ERR = 20,    // lpull_passes -> run_lpull_batch: the error word as of the last pass read ...
+  HP_LP_BATCH = 21,  // [2] ... and a no-log batch's words LP_CT_TMAX, LP_CT_DELIV
+  HP_LP_SET = 24,    // [2] part_lp_set's records and min pending key on their way to the device
+  HP_SEED_MIN = 28,  // part_lp_begin -> part_lp_seed_min
+  HP_LAT_ERR = 30,   // part_lat_stage -> part_lat_err
+  HP_GATHER_WORDS = 4
+};
+static_assert(C_COUNT <= HP_SCRATCH && PS_SLOTS * PS_WORDS <= HP_SCRATCH, "a call's read-back stays in the scratch");
+static_assert(HP_GATHER + HP_GATHER_WORDS <= HP_LP_ERR && HP_LP_ERR < HP_LP_BATCH && HP_LP_BATCH + 2 <= HP_LP_SET &&
+                  HP_LP_SET + 2 <= HP_SEED_MIN && HP_SEED_MIN < HP_LAT_ERR && HP_LAT_ERR < H_PINNED_WORDS,
+              "the named words of h_pinned are apart and inside it");
 
 // Per-batch geometry (gs_relax.hip setup_batch).
 struct Batch {
@@ -248,7 +291,7 @@ struct Ctx {
   uint32_t text_par = 0;
   bool text_busy = false;
   // gs_run_partitioned's latencies (part_lat_stage): d_lat_t holds the batch's message-major
-  // latencies and the error word is on its way to h_pinned[30] (deliver skips both steps)
+  // latencies and the error word is on its way to h_pinned[HP_LAT_ERR] (deliver skips both steps)
   bool lat_staged = false;
   DevBuf<uint64_t> d_lr_tpub;  // [B] a message-sharded batch's publish times and publishers (k_lat_rows)
   DevBuf<uint32_t> d_lr_pub;
@@ -274,7 +317,7 @@ struct Ctx {
   bool keys_log = false;       // keys hold the list pull path's final logs (not dense rows): k_lcomplete
   bool keys_none = false;      // the last batch ran the no-log list pass: keys hold neither rows nor logs
   uint32_t mesh_dmax = 0;      // widest frozen-mesh row (list pull ring bound); 0 = not known
-  DevBuf<uint64_t> d_pctrl;  // [3][4] pass control slots (gs_run's list pass: and its two batch words, LP_CT_WORDS)
+  DevBuf<uint64_t> d_pctrl;  // [PS_SLOTS][PS_WORDS] pass control slots, then the no-log pass's batch words (LP_CT_WORDS)
   // list pull path (gs_lpull_kernel.h)
   DevBuf<uint64_t> d_lblk;   // [K][N][L] candidate lists per destination-window slot
   DevBuf<uint32_t> d_lst;    // [N][16] list lengths per destination window, final-log length
@@ -286,7 +329,7 @@ struct Ctx {
   DevBuf<uint16_t> d_flane;  // [N][L] lanes of the final log
   DevBuf<uint64_t> d_counters;  // [C_COUNT]
   DevBuf<uint64_t> d_cnt_save;  // [C_COUNT] counters before a batch (gossip fallback restores them)
-  uint64_t* h_pinned = nullptr; // pinned host mirror of ctrl + counters (H_PINNED_WORDS)
+  uint64_t* h_pinned = nullptr; // pinned host mirror of ctrl + counters (H_PINNED_WORDS; the HP_ words above)
   // per-message reductions of k_complete / k_pct (gs_relax.hip)
   DevBuf<uint64_t> d_mstat;     // [B][MS_COLS]
   DevBuf<uint32_t> d_hist;      // [B][GS_HIST_BINS]

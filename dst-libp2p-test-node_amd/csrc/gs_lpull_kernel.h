@@ -2428,13 +2428,7 @@ void lpull_launch_fp(const LPullArgs& a, unsigned grid, hipStream_t s) {
 }
 template <bool... FL>
 void lpull_launch(uint32_t FP, const LPullArgs& a, unsigned grid, hipStream_t s) {
-  switch (FP) {
-    case 1: return lpull_launch_fp<1, FL...>(a, grid, s);
-    case 2: return lpull_launch_fp<2, FL...>(a, grid, s);
-    case 4: return lpull_launch_fp<4, FL...>(a, grid, s);
-    case 8: return lpull_launch_fp<8, FL...>(a, grid, s);
-    default: return lpull_launch_fp<16, FL...>(a, grid, s);
-  }
+  with_fp(FP, [&](auto fp) { lpull_launch_fp<fp.value, FL...>(a, grid, s); });
 }
 
 // One pass of a batch on the whole graph (a peer-partitioned batch's pass is

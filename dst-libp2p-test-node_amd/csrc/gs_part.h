@@ -331,17 +331,6 @@ __global__ __launch_bounds__(TB) void k_lat_rows(const uint64_t* __restrict__ tc
   lat_t[i] = (uint16_t)v;
 }
 
-template <int FP>
-void part_export_fp(const RelaxArgs& a, unsigned grid, hipStream_t s, gs_part_record* rec, uint64_t cap,
-                    uint64_t* pcnt) {
-  k_pexport<FP><<<grid, TB, 0, s>>>(a, rec, cap, pcnt);
-}
-template <int FP>
-void part_recv_fp(const RelaxArgs& a, unsigned grid, hipStream_t s, const gs_part_record* rec, uint64_t n,
-                  uint64_t* pcnt) {
-  k_precv<FP><<<grid, TB, 0, s>>>(a, rec, n, pcnt);
-}
-
 RelaxArgs part_args(Ctx& c) {
   const Batch& b = c.part_b;
   RelaxArgs ra{};
@@ -356,6 +345,17 @@ RelaxArgs part_args(Ctx& c) {
   ra.launch = 0;
   ra.u0 = c.part_u0;
   return ra;
+}
+
+// k_scan of the bucket in ctrl[0] over the part's rows.
+void part_scan_launch(Ctx& c, const RelaxArgs& ra) {
+  with_fp(c.part_b.FP, [&](auto fp) { k_scan<fp.value, false, false><<<c.part_grid, TB, 0, c.stream>>>(ra); });
+}
+
+// n received records into the part's own peers (k_precv).
+void part_recv_launch(Ctx& c, const RelaxArgs& ra, const gs_part_record* rec, uint64_t n) {
+  const unsigned grid = (unsigned)std::min<uint64_t>((n + TB - 1) / TB, (uint64_t)c.num_cus * 16);
+  with_fp(c.part_b.FP, [&](auto fp) { k_precv<fp.value><<<grid, TB, 0, c.stream>>>(ra, rec, n, c.d_pcnt.p); });
 }
 
 }  // namespace
@@ -444,13 +444,7 @@ bool part_scan(Ctx& c, uint64_t bucket_key, gs_part_record* rec, uint64_t cap, u
   const unsigned grid = c.part_grid;
   const uint32_t nwaves = grid * (TB / 64);
   k_pbucket<<<1, 64, 0, s>>>(c.d_ctrl.p, c.d_pcnt.p, bucket_key);
-  switch (b.FP) {
-    case 1: k_scan<1, false, false><<<grid, TB, 0, s>>>(ra); break;
-    case 2: k_scan<2, false, false><<<grid, TB, 0, s>>>(ra); break;
-    case 4: k_scan<4, false, false><<<grid, TB, 0, s>>>(ra); break;
-    case 8: k_scan<8, false, false><<<grid, TB, 0, s>>>(ra); break;
-    default: k_scan<16, false, false><<<grid, TB, 0, s>>>(ra); break;
-  }
+  part_scan_launch(c, ra);
   k_pcount<<<std::min<uint32_t>(64, (nwaves + TB - 1) / TB), TB, 0, s>>>(c.d_fr_cnt.p, nwaves, c.d_pcnt.p);
   GS_HIP(hipGetLastError());
   GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_ctrl.p + 1, 8, hipMemcpyDeviceToHost, s));
@@ -465,13 +459,7 @@ bool part_scan(Ctx& c, uint64_t bucket_key, gs_part_record* rec, uint64_t cap, u
   }
   if (need) {
     if (!rec) c.fail(GS_EINVAL, "null record buffer");
-    switch (b.FP) {
-      case 1: part_export_fp<1>(ra, grid, s, rec, cap, c.d_pcnt.p); break;
-      case 2: part_export_fp<2>(ra, grid, s, rec, cap, c.d_pcnt.p); break;
-      case 4: part_export_fp<4>(ra, grid, s, rec, cap, c.d_pcnt.p); break;
-      case 8: part_export_fp<8>(ra, grid, s, rec, cap, c.d_pcnt.p); break;
-      default: part_export_fp<16>(ra, grid, s, rec, cap, c.d_pcnt.p); break;
-    }
+    with_fp(b.FP, [&](auto fp) { k_pexport<fp.value><<<grid, TB, 0, s>>>(ra, rec, cap, c.d_pcnt.p); });
     GS_HIP(hipGetLastError());
   }
   GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_pcnt.p + 1, 8, hipMemcpyDeviceToHost, s));
@@ -486,17 +474,8 @@ uint64_t part_relax(Ctx& c, uint64_t bucket_key, const gs_part_record* rec, uint
   if (n == 0) return INF64;
   if (!rec) c.fail(GS_EINVAL, "null record buffer");
   hipStream_t s = c.stream;
-  const Batch& b = c.part_b;
-  const RelaxArgs ra = part_args(c);
   GS_HIP(hipMemsetAsync(c.d_pcnt.p + 2, 0xFF, 8, s));
-  const unsigned grid = (unsigned)std::min<uint64_t>((n + TB - 1) / TB, (uint64_t)c.num_cus * 16);
-  switch (b.FP) {
-    case 1: part_recv_fp<1>(ra, grid, s, rec, n, c.d_pcnt.p); break;
-    case 2: part_recv_fp<2>(ra, grid, s, rec, n, c.d_pcnt.p); break;
-    case 4: part_recv_fp<4>(ra, grid, s, rec, n, c.d_pcnt.p); break;
-    case 8: part_recv_fp<8>(ra, grid, s, rec, n, c.d_pcnt.p); break;
-    default: part_recv_fp<16>(ra, grid, s, rec, n, c.d_pcnt.p); break;
-  }
+  part_recv_launch(c, part_args(c), rec, n);
   GS_HIP(hipGetLastError());
   GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_pcnt.p + 2, 8, hipMemcpyDeviceToHost, s));
   GS_HIP(hipStreamSynchronize(s));
@@ -520,64 +499,30 @@ void part_dev_bucket(Ctx& c, uint32_t parts) {
 
 // k_scan of the bucket in ctrl[0] + the per-destination record counts (d_dcnt).
 void part_dev_scan_count(Ctx& c, uint32_t parts) {
-  hipStream_t s = c.stream;
-  const Batch& b = c.part_b;
   const RelaxArgs ra = part_args(c);
-  const unsigned grid = c.part_grid;
-  switch (b.FP) {
-    case 1: k_scan<1, false, false><<<grid, TB, 0, s>>>(ra); break;
-    case 2: k_scan<2, false, false><<<grid, TB, 0, s>>>(ra); break;
-    case 4: k_scan<4, false, false><<<grid, TB, 0, s>>>(ra); break;
-    case 8: k_scan<8, false, false><<<grid, TB, 0, s>>>(ra); break;
-    default: k_scan<16, false, false><<<grid, TB, 0, s>>>(ra); break;
-  }
-#define GS_PCOUNT(F) k_pexport_dest<F, true><<<grid, TB, 0, s>>>(ra, nullptr, c.d_dcnt.p, c.d_dpos.p, parts, c.cfg.peers)
-  switch (b.FP) {
-    case 1: GS_PCOUNT(1); break;
-    case 2: GS_PCOUNT(2); break;
-    case 4: GS_PCOUNT(4); break;
-    case 8: GS_PCOUNT(8); break;
-    default: GS_PCOUNT(16); break;
-  }
-#undef GS_PCOUNT
+  const uint32_t N = c.cfg.peers;
+  part_scan_launch(c, ra);
+  with_fp(c.part_b.FP, [&](auto fp) {
+    k_pexport_dest<fp.value, true><<<c.part_grid, TB, 0, c.stream>>>(ra, nullptr, c.d_dcnt.p, c.d_dpos.p, parts, N);
+  });
   GS_HIP(hipGetLastError());
   c.stats.relax_launches++;
 }
 
 // The records, grouped by destination part (offsets = prefix of d_dcnt).
 void part_dev_export(Ctx& c, uint32_t parts, gs_part_record* out) {
-  hipStream_t s = c.stream;
-  const Batch& b = c.part_b;
   const RelaxArgs ra = part_args(c);
-  const unsigned grid = c.part_grid;
-#define GS_PEXP(F) k_pexport_dest<F, false><<<grid, TB, 0, s>>>(ra, out, c.d_dcnt.p, c.d_dpos.p, parts, c.cfg.peers)
-  switch (b.FP) {
-    case 1: GS_PEXP(1); break;
-    case 2: GS_PEXP(2); break;
-    case 4: GS_PEXP(4); break;
-    case 8: GS_PEXP(8); break;
-    default: GS_PEXP(16); break;
-  }
-#undef GS_PEXP
+  const uint32_t N = c.cfg.peers;
+  with_fp(c.part_b.FP, [&](auto fp) {
+    k_pexport_dest<fp.value, false><<<c.part_grid, TB, 0, c.stream>>>(ra, out, c.d_dcnt.p, c.d_dpos.p, parts, N);
+  });
   GS_HIP(hipGetLastError());
 }
 
 // Received records into own peers, then this part's next-bucket candidate in ctrl[0].
 void part_dev_relax_next(Ctx& c, const gs_part_record* in, uint64_t n) {
-  hipStream_t s = c.stream;
-  const Batch& b = c.part_b;
-  if (n) {
-    const RelaxArgs ra = part_args(c);
-    const unsigned grid = (unsigned)std::min<uint64_t>((n + TB - 1) / TB, (uint64_t)c.num_cus * 16);
-    switch (b.FP) {
-      case 1: part_recv_fp<1>(ra, grid, s, in, n, c.d_pcnt.p); break;
-      case 2: part_recv_fp<2>(ra, grid, s, in, n, c.d_pcnt.p); break;
-      case 4: part_recv_fp<4>(ra, grid, s, in, n, c.d_pcnt.p); break;
-      case 8: part_recv_fp<8>(ra, grid, s, in, n, c.d_pcnt.p); break;
-      default: part_recv_fp<16>(ra, grid, s, in, n, c.d_pcnt.p); break;
-    }
-  }
-  k_pnext<<<1, 64, 0, s>>>(c.d_ctrl.p, c.d_pcnt.p);
+  if (n) part_recv_launch(c, part_args(c), in, n);
+  k_pnext<<<1, 64, 0, c.stream>>>(c.d_ctrl.p, c.d_pcnt.p);
   GS_HIP(hipGetLastError());
 }
 
@@ -609,11 +554,7 @@ static bool part_dev_complete_check(Ctx& c) {
   GS_HIP(hipStreamSynchronize(c.stream));
   const uint64_t* ms = c.h_slms;
   std::vector<uint64_t> rel0(b.B);
-  const uint64_t hb = c.cfg.heartbeat_ns, ph = c.cfg.hb_phase_ns;
-  for (uint32_t q = 0; q < b.B; q++) {
-    const uint64_t tp = b.tpub[q], h0 = tp <= ph ? 0 : (tp - ph + hb - 1) / hb;
-    rel0[q] = ph + h0 * hb - tp;
-  }
+  for (uint32_t q = 0; q < b.B; q++) rel0[q] = hb_pos(c, b.tpub[q]).rel0;
   const bool ok = gossip_noop(b, ms, rel0);
   if (!ok)
     for (uint32_t q = 0; q < b.B; q++) {
@@ -657,7 +598,7 @@ void part_abort(Ctx& c) {
 // peer-major d_lat, or for a message-sharded batch (ms_sched: its B schedule rows) from the
 // exchanged d_tc_t by k_lat_rows — then the delay accumulators' share of the batch
 // (gs_set_peer_delay: the own rows, once) and, when the latencies leave as text, the line counters'
-// room for the batch (k_lt_room), and the error word on its way into h_pinned[30].
+// room for the batch (k_lt_room), and the error word on its way into h_pinned[HP_LAT_ERR].
 void part_lat_stage(Ctx& c, uint32_t B, const gs_publish* ms_sched) {
   hipStream_t s = c.stream;
   const uint32_t un = c.part_un;
@@ -691,13 +632,13 @@ void part_lat_stage(Ctx& c, uint32_t B, const gs_publish* ms_sched) {
                                                                                    c.d_counters.p);
     GS_HIP(hipGetLastError());
   }
-  GS_HIP(hipMemcpyAsync(c.h_pinned + 30, c.d_counters.p + C_ERR, 8, hipMemcpyDeviceToHost, s));
+  GS_HIP(hipMemcpyAsync(c.h_pinned + HP_LAT_ERR, c.d_counters.p + C_ERR, 8, hipMemcpyDeviceToHost, s));
   c.lat_staged = true;
 }
 
 uint64_t part_lat_err(Ctx& c) {
   GS_HIP(hipStreamSynchronize(c.stream));
-  return c.h_pinned[30] & (ERR_LAT16 | ERR_LINES);
+  return c.h_pinned[HP_LAT_ERR] & (ERR_LAT16 | ERR_LINES);
 }
 
 // A staged message-sharded batch into the sink: its text, or the rows / on_lat blocks
@@ -719,11 +660,7 @@ void part_finish(Ctx& c, const gs_result_sink* sink) {
     std::vector<uint64_t> ms((size_t)b.B * MS_COLS), rel0(b.B);
     GS_HIP(hipMemcpyAsync(ms.data(), c.d_mstat.p, ms.size() * 8, hipMemcpyDeviceToHost, c.stream));
     GS_HIP(hipStreamSynchronize(c.stream));
-    const uint64_t hb = c.cfg.heartbeat_ns, ph = c.cfg.hb_phase_ns;
-    for (uint32_t q = 0; q < b.B; q++) {
-      const uint64_t tp = b.tpub[q], h0 = tp <= ph ? 0 : (tp - ph + hb - 1) / hb;
-      rel0[q] = ph + h0 * hb - tp;
-    }
+    for (uint32_t q = 0; q < b.B; q++) rel0[q] = hb_pos(c, b.tpub[q]).rel0;
     if (!gossip_noop(b, ms.data(), rel0))
       c.fail(GS_EUNSUPPORTED, "lazy gossip can change this batch (an IHAVE lands before the last delivery); "
                               "partitioned mode runs eager forwarding only: use gs_run");
@@ -742,31 +679,27 @@ void part_finish(Ctx& c, const gs_result_sink* sink) {
 // per-peer counts and offsets are exchanged (gs_comm.hip), so that the next
 // pass reads any neighbour's records exactly as gs_run's pass does.
 
+// What gs_run's list-pass set-up (lpull_begin, lpull_args, lpull_seed) needs to know of a part:
+// its rows are peers [u0, u0 + un), read through the exchange buffers. A part always keeps its
+// final log (no no-log form) and takes no IDONTWANT, gossip-active or churn batch (part_check).
+static LpOpts part_lp_opts(const Ctx& c) {
+  LpOpts o;
+  o.part = true;
+  o.u0 = c.part_u0;
+  return o;
+}
 static LPullArgs part_lp_args(Ctx& c) {
-  const Batch& b = c.part_b;
-  const uint32_t un = c.part_un, L = b.L;
-  LPullArgs la{};
-  la.keys = c.d_keys.p; la.flane = c.d_flane.p; la.busy = c.d_busy.p; la.blk = c.d_lblk.p;
-  la.st = c.d_lst.p; la.fin = c.d_lfin.p; la.lrec = c.d_lrec.p; la.lcnt = c.d_lcnt.p;
-  la.rpos = c.d_rpos.p; la.mesh = c.d_mesh.p; la.pub = c.d_pub.p; la.stage = c.d_stage.p;
-  la.tables = c.d_tables.p; la.ctrl = c.d_pctrl.p; la.counters = c.d_counters.p;
-  const uint64_t grain = pull_grain(b.tshift);
-  la.delta = b.delta / grain * grain;
-  la.tmax = b.tmax - grain;
-  la.N = un; la.B = b.B; la.L = L; la.S = c.S; la.sb = b.sb; la.tshift = b.tshift;
-  la.K = c.part_lpK; la.lb = c.part_lplb; la.dG = (uint32_t)(la.delta / grain);
-  la.ls = lpull_stride(b);
-  la.lcap = (uint32_t)std::min<long>(std::max(1l, env_int("GS_LPULL_CAP", (long)la.ls)), (long)la.ls);
-  la.u0 = c.part_u0;
-  la.rmax = lpull_rmax(b);
-  la.rpk = c.d_rpk.p; la.roff = c.d_roffg.p; la.rcg = c.d_rcg.p;
+  LPullArgs la = lpull_args(c, c.part_b, c.part_lpK, c.part_lplb, part_lp_opts(c), c.part_un);
   la.pass = c.part_lppass;
   return la;
 }
 
+// The slot the last pass wrote and the next one decides from (the seeds': slot 2 before pass 0;
+// lockstep parts: the same in each).
+static uint32_t part_lp_slot(const Ctx& c) { return (c.part_lppass + 2) % PS_SLOTS; }
+
 bool part_lp_begin(Ctx& c, const gs_publish* sched, uint64_t n_msgs) {
-  const uint32_t F = part_check(c, sched, n_msgs);
-  (void)F;
+  part_check(c, sched, n_msgs);
   // without bit 64 (or with GS_PART_PUSH) the push protocol runs
   if (!path_knob().list || getenv("GS_PART_PUSH")) return false;
   hipStream_t s = c.stream;
@@ -775,61 +708,32 @@ bool part_lp_begin(Ctx& c, const gs_publish* sched, uint64_t n_msgs) {
   const uint32_t N = c.cfg.peers, un = c.part_un, Bmax = c.cfg.batch;
   c.part_b = setup_batch(c, sched, 0, n_msgs);
   const Batch& b = c.part_b;
-  if (b.L > PULL_LMAX || b.delta < pull_grain(b.tshift)) return false;
-  uint32_t lb = 0;
   const uint64_t grain = pull_grain(b.tshift);
-  const uint32_t K = lpull_ring(c, b, b.delta / grain * grain, &lb);
-  if (!K) return false;
-  c.part_lpK = K;
-  c.part_lplb = lb;
+  if (b.L > PULL_LMAX || b.delta < grain) return false;
+  c.part_lpK = lpull_ring(c, b, b.delta / grain * grain, &c.part_lplb);
+  if (!c.part_lpK) return false;
   c.part_lppass = 0;
-  const size_t NL = (size_t)un * b.L;
-  const uint32_t ls = lpull_stride(b);
-  c.d_keys.alloc(NL);
-  c.d_flane.alloc(NL);
-  c.d_lrec.alloc(2 * NL);
-  c.d_lcnt.alloc(2 * (size_t)un);
-  c.d_lblk.alloc((size_t)K * un * ls);
-  c.d_lst.alloc((size_t)un * LP_SW);
-  c.d_lfin.alloc((size_t)un * LP_FW);
-  c.d_pctrl.alloc(12);
+  // the part's own: its rows' keys (logs) and results, the uplink FIFOs, the exchange tables
+  c.d_keys.alloc((size_t)un * b.L);
+  c.d_tc.alloc((size_t)un * Bmax);
+  c.d_hops.alloc((size_t)un * Bmax);
   c.d_rcg.alloc(N);
   c.d_roffg.alloc(N);
   c.d_rpk.alloc(1);
   c.d_pkcur.alloc(1);
-  if (b.FP > 1) c.d_busy.alloc((size_t)un * Bmax);
-  c.d_tc.alloc((size_t)un * Bmax);
-  c.d_hops.alloc((size_t)un * Bmax);
-  if (!c.rpos_valid) {
-    c.d_rpos.alloc((size_t)N * MESH_W);
-    k_rpos<<<(unsigned)(((uint64_t)N * MESH_W + TB - 1) / TB), TB, 0, s>>>(c.d_mesh.p, c.d_rpos.p, N, c.d_counters.p);
-    GS_HIP(hipGetLastError());
-    if (read_counter(c, C_ERR) & ERR_MESH) c.fail(GS_ERANGE, "mesh is not symmetric");
-    c.rpos_valid = true;
-  }
   c.keys_log = c.keys_none = false;
-  if (b.FP > 1) GS_HIP(hipMemsetAsync(c.d_busy.p, 0, (size_t)un * b.B * 8, s));
-  GS_HIP(hipMemsetAsync(c.d_lst.p, 0, (size_t)un * LP_SW * 4, s));
-  GS_HIP(hipMemsetAsync(c.d_lfin.p, 0, (size_t)un * LP_FW * 4, s));
-  GS_HIP(hipMemsetAsync(c.d_pctrl.p, 0, 12 * 8, s));
-  for (int q = 0; q < 3; q++) GS_HIP(hipMemsetAsync(c.d_pctrl.p + q * 4 + 3, 0xFF, 8, s));
-  c.d_lp_save.alloc(C_COUNT);
-  GS_HIP(hipMemcpyAsync(c.d_lp_save.p, c.d_counters.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
-  const uint64_t scap = (uint64_t)b.B * b.Fe * std::max<uint64_t>(c.max_degree, MESH_W);
-  c.d_skey.alloc(scap);
-  c.d_slane.alloc(scap);
-  c.d_scnt.alloc(1);
-  GS_HIP(hipMemsetAsync(c.d_scnt.p, 0, 4, s));
-  launch_seed(c, b, c.part_u0, un, c.d_pctrl.p + 2 * 4 + 3, nullptr, true);
-  const LPullArgs la = part_lp_args(c);
-  k_lseed<<<(unsigned)std::max<uint64_t>(1, std::min<uint64_t>((scap + TB - 1) / TB, (uint64_t)c.num_cus * 4)), TB, 0,
-            s>>>(la, c.d_skey.p, c.d_slane.p, c.d_scnt.p);
-  k_lpub<<<(b.B * b.Fe + 255) / 256, 256, 0, s>>>(la, b.Fe);
-  GS_HIP(hipGetLastError());
+  if (b.FP > 1) {
+    c.d_busy.alloc((size_t)un * Bmax);
+    GS_HIP(hipMemsetAsync(c.d_busy.p, 0, (size_t)un * b.B * 8, s));
+  }
+  const LpOpts o = part_lp_opts(c);
+  lpull_begin(c, b, c.part_lpK, o, un);
+  LPullArgs la = part_lp_args(c);
+  lpull_seed(c, b, o, la);
   c.part_lpgrid = lpull_grid(un, c.num_cus);  // by the rows this part owns
-  // the seeds' min key lands in pinned word 28; part_lp_seed_min waits for it
+  // the seeds' min key on its way to the host; part_lp_seed_min waits for it
   // (the caller begins every part first, so that their setups overlap)
-  GS_HIP(hipMemcpyAsync(c.h_pinned + 28, c.d_pctrl.p + 2 * 4 + 3, 8, hipMemcpyDeviceToHost, s));
+  GS_HIP(hipMemcpyAsync(c.h_pinned + HP_SEED_MIN, c.d_pctrl.p + PS_SEED_MIN, 8, hipMemcpyDeviceToHost, s));
   c.part_lp = true;
   c.part_open = true;
   return true;
@@ -837,17 +741,18 @@ bool part_lp_begin(Ctx& c, const gs_publish* sched, uint64_t n_msgs) {
 
 uint64_t part_lp_seed_min(Ctx& c) {
   GS_HIP(hipStreamSynchronize(c.stream));
-  return c.h_pinned[28];
+  return c.h_pinned[HP_SEED_MIN];
 }
 
 // The combined pass control into the slot the next pass decides from (slot of the last pass).
 void part_lp_set(Ctx& c, uint64_t records, uint64_t minp) {
-  const uint32_t slot = (c.part_lppass + 2) % 3;  // the last pass's slot (seeds: slot 2 before pass 0)
-  c.h_pinned[24] = records;
-  c.h_pinned[25] = minp;
+  static_assert(PS_MIN == PS_RECORDS + 1, "one copy for both words");
+  c.h_pinned[HP_LP_SET] = records;
+  c.h_pinned[HP_LP_SET + 1] = minp;
   // (no wait: the staging words are next written by the next part_lp_set,
   // after part_lp_read has drained this stream)
-  GS_HIP(hipMemcpyAsync(c.d_pctrl.p + slot * 4 + 2, c.h_pinned + 24, 16, hipMemcpyHostToDevice, c.stream));
+  GS_HIP(hipMemcpyAsync(c.d_pctrl.p + part_lp_slot(c) * PS_WORDS + PS_RECORDS, c.h_pinned + HP_LP_SET, 16,
+                        hipMemcpyHostToDevice, c.stream));
 }
 
 void part_lp_pass(Ctx& c) {
@@ -861,17 +766,17 @@ void part_lp_pass(Ctx& c) {
 // The last pass's control words into pinned memory (enqueued), then waited
 // for: several parts' reads in flight together.
 void part_lp_read_enqueue(Ctx& c) {
-  const uint32_t slot = (c.part_lppass + 2) % 3;
-  GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_pctrl.p + slot * 4, 32, hipMemcpyDeviceToHost, c.stream));
-  GS_HIP(hipMemcpyAsync(c.h_pinned + 4, c.d_counters.p + C_ERR, 8, hipMemcpyDeviceToHost, c.stream));
+  GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_pctrl.p + part_lp_slot(c) * PS_WORDS, PS_WORDS * 8, hipMemcpyDeviceToHost,
+                        c.stream));
+  GS_HIP(hipMemcpyAsync(c.h_pinned + PS_WORDS, c.d_counters.p + C_ERR, 8, hipMemcpyDeviceToHost, c.stream));
 }
 
 void part_lp_read_wait(Ctx& c, uint64_t out[4]) {
   GS_HIP(hipStreamSynchronize(c.stream));
-  out[0] = c.h_pinned[1];
-  out[1] = c.h_pinned[2];
-  out[2] = c.h_pinned[3];
-  out[3] = c.h_pinned[4];
+  out[0] = c.h_pinned[PS_MODE];
+  out[1] = c.h_pinned[PS_RECORDS];
+  out[2] = c.h_pinned[PS_MIN];
+  out[3] = c.h_pinned[PS_WORDS];  // (the error word, behind the slot)
 }
 
 void part_lp_read(Ctx& c, uint64_t out[4]) {
@@ -879,17 +784,26 @@ void part_lp_read(Ctx& c, uint64_t out[4]) {
   part_lp_read_wait(c, out);
 }
 
+// What a pack of the last pass's records reads: the halves of the record and count double
+// buffers that pass wrote (lrec / lcnt [pass & 1]); the pack kernels' grid over the part's rows.
+struct LastPass {
+  const uint64_t* rec;
+  const uint32_t* cnt;
+  unsigned grid;
+};
+static LastPass part_lp_last(const Ctx& c) {
+  const uint32_t un = c.part_un, nb = (c.part_lppass + 1) & 1;
+  return {c.d_lrec.p + (size_t)nb * un * c.part_b.L, c.d_lcnt.p + (size_t)nb * un,
+          (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)un + 255) / 256, (uint64_t)c.num_cus * 8))};
+}
+
 void part_lp_pack(Ctx& c, uint64_t base, uint64_t mine) {
-  const uint32_t un = c.part_un, L = c.part_b.L;
   (void)mine;  // the caller sized d_rpk for every part's records
   hipStream_t s = c.stream;
   GS_HIP(hipMemsetAsync(c.d_pkcur.p, 0, 8, s));
-  const uint32_t nb = (c.part_lppass + 1) & 1;  // the last pass wrote lrec / lcnt [pass & 1]
-  const unsigned grid = (unsigned)std::max<uint64_t>(
-      1, std::min<uint64_t>(((uint64_t)un + 255) / 256, (uint64_t)c.num_cus * 8));
-  k_lpack<<<grid, TB, 0, s>>>(c.d_lrec.p + (size_t)nb * un * L, c.d_lcnt.p + (size_t)nb * un, un, L, base,
-                              c.d_rpk.p + base, c.d_roffg.p + c.part_u0, c.d_rcg.p + c.part_u0,
-                              (unsigned long long*)c.d_pkcur.p);
+  const LastPass lp = part_lp_last(c);
+  k_lpack<<<lp.grid, TB, 0, s>>>(lp.rec, lp.cnt, c.part_un, c.part_b.L, base, c.d_rpk.p + base,
+                                 c.d_roffg.p + c.part_u0, c.d_rcg.p + c.part_u0, (unsigned long long*)c.d_pkcur.p);
   GS_HIP(hipGetLastError());
 }
 
@@ -901,15 +815,13 @@ void part_lp_route_launch(Ctx& c, uint32_t P, uint32_t me, const RouteDst& dst) 
   hipStream_t s = c.stream;
   c.d_pkcur.alloc(P);
   GS_HIP(hipMemsetAsync(c.d_pkcur.p, 0, (size_t)P * 8, s));
-  const uint32_t nb = (c.part_lppass + 1) & 1;  // the last pass wrote lrec / lcnt [pass & 1]
-  const unsigned grid = (unsigned)std::max<uint64_t>(
-      1, std::min<uint64_t>(((uint64_t)un + 255) / 256, (uint64_t)c.num_cus * 8));
+  const LastPass lp = part_lp_last(c);
   RouteLo rl{};
   const PartLayout lay{P, c.cfg.peers, 0};
   for (uint32_t q = 0; q < P && q < LP_PMAX; q++) rl.lo[q] = lay.u0(q);
 #define GS_LPR(PM)                                                                                             \
-  k_lpack_route<PM><<<grid, TB, 0, s>>>(c.d_lrec.p + (size_t)nb * un * L, c.d_lcnt.p + (size_t)nb * un, c.d_mesh.p, \
-                                        c.part_u0, un, L, P, me, (unsigned long long*)c.d_pkcur.p, rl, dst)
+  k_lpack_route<PM><<<lp.grid, TB, 0, s>>>(lp.rec, lp.cnt, c.d_mesh.p, c.part_u0, un, L, P, me,                \
+                                           (unsigned long long*)c.d_pkcur.p, rl, dst)
   if (P <= 4) GS_LPR(4);
   else if (P <= 8) GS_LPR(8);
   else GS_LPR(16);
@@ -921,9 +833,7 @@ void part_lp_route_launch(Ctx& c, uint32_t P, uint32_t me, const RouteDst& dst) 
 // nb, rows of L): their offsets from d_rpk's base, as 64-bit element offsets
 // modulo 2^64 (the pass adds them to the same base). d_rpk is sized before.
 static void part_lp_own_inplace(Ctx& c, RouteDst& d) {
-  const uint32_t un = c.part_un, L = c.part_b.L;
-  const uint32_t nb = (c.part_lppass + 1) & 1;
-  const uint64_t* rows = c.d_lrec.p + (size_t)nb * un * L;
+  const uint64_t* rows = part_lp_last(c).rec;
   d.own_off = (uint64_t)(((intptr_t)rows - (intptr_t)c.d_rpk.p) / 8);  // (both 8-B aligned; may be negative)
   d.own_inplace = 1;
 }
@@ -987,8 +897,7 @@ void part_lp_combine(Ctx** cx, uint32_t P, uint64_t* st) {
   }
   c0.d_pstat.alloc((size_t)P * 4);
   if (!c0.h_pstat) GS_HIP(hipHostMalloc((void**)&c0.h_pstat, LP_PMAX * 4 * 8, hipHostMallocDefault));
-  const uint32_t slot = (c0.part_lppass + 2) % 3;  // the last pass's slot (lockstep parts: the same in each)
-  k_part_combine<<<1, 64, 0, c0.stream>>>(pc, P, slot, c0.d_pstat.p);
+  k_part_combine<<<1, 64, 0, c0.stream>>>(pc, P, part_lp_slot(c0), c0.d_pstat.p);
   GS_HIP(hipGetLastError());
   GS_HIP(hipMemcpyAsync(c0.h_pstat, c0.d_pstat.p, (size_t)P * 4 * 8, hipMemcpyDeviceToHost, c0.stream));
   GS_HIP(hipStreamSynchronize(c0.stream));
@@ -997,6 +906,7 @@ void part_lp_combine(Ctx** cx, uint32_t P, uint64_t* st) {
 
 // The routed records per destination (counts[q]) of the last pack.
 void part_lp_route_read(Ctx& c, uint32_t P, uint64_t* counts) {
+  static_assert(LP_PMAX <= HP_SCRATCH, "a count per destination part in the mirror's scratch words");
   GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_pkcur.p, (size_t)P * 8, hipMemcpyDeviceToHost, c.stream));
   GS_HIP(hipStreamSynchronize(c.stream));
   memcpy(counts, c.h_pinned, (size_t)P * 8);
@@ -1017,7 +927,7 @@ void part_lp_route_fix(Ctx& c, uint32_t P, uint32_t me, const uint64_t* base) {
 // (k_lfinal -> dense rows -> k_complete).
 void part_lp_end_enqueue(Ctx& c, const gs_result_sink* sink) {
   const SinkWants w = sink_wants(c, sink);
-  const bool dense = w.rows() || w.summary || c.part_b.FP > 1 || getenv("GS_LPULL_DENSE");
+  const bool dense = dense_rows(c, w, false) || c.part_b.FP > 1;
   if (dense) {
     const LPullArgs la = part_lp_args(c);
     k_lfinal<<<c.part_lpgrid, TB, 0, c.stream>>>(la);  // final logs -> dense rows of own peers

@@ -116,7 +116,7 @@ struct PRun {
     if (any) throw Error(GS_EINVAL, "another rank failed this partitioned call");
   }
 
-  // Every rank's n words (n <= 4) -> out[rank * n + k] on the host, through the
+  // Every rank's n words (n <= HP_GATHER_WORDS) -> out[rank * n + k] on the host, through the
   // scratch's control rows; loop-back: the one row is the caller's. Returns the rows.
   uint32_t gather(const uint64_t* mine, uint32_t n, uint64_t* out) {
     if (cm->local) {
@@ -125,8 +125,8 @@ struct PRun {
     }
     Ctx& c = *cx[0];
     uint64_t* w = cm->scratch_ctl();
-    memcpy(c.h_pinned + 16, mine, n * 8);
-    GS_HIP(hipMemcpyAsync(w + (size_t)cm->rank * n, c.h_pinned + 16, n * 8, hipMemcpyHostToDevice, c.stream));
+    memcpy(c.h_pinned + HP_GATHER, mine, n * 8);
+    GS_HIP(hipMemcpyAsync(w + (size_t)cm->rank * n, c.h_pinned + HP_GATHER, n * 8, hipMemcpyHostToDevice, c.stream));
     coll_AllGather(cm, w + (size_t)cm->rank * n, w, n, ncclUint64, c.stream);
     std::vector<uint64_t> h((size_t)cm->nranks * n);
     GS_HIP(hipMemcpyAsync(h.data(), w, h.size() * 8, hipMemcpyDeviceToHost, c.stream));
@@ -203,6 +203,7 @@ struct PRun {
     }
     const uint64_t sig[8] = {c.cfg.peers, c.cfg.batch, c.cfg.lazy_gossip, c.cfg.idontwant,
                              c.cfg.churn_ppm, c.cfg.fragments, c.cfg.seed, h ^ n_msgs};
+    static_assert(2 * sizeof sig <= HP_SCRATCH * 8, "the MIN and MAX rows in the mirror's scratch words");
     DevBuf<uint64_t> d;
     d.alloc(16);
     memcpy(c.h_pinned, sig, sizeof sig);
@@ -409,7 +410,7 @@ struct PRun {
         err |= st[(size_t)p * 4 + 3];
       }
       if (err & (ERR_LIST | ERR_RING)) return lp_abort();  // lost entries somewhere: the push protocol takes the batch
-      if (st[0] == 0) break;  // pass mode DONE (PM_DONE, gs_pull_kernel.h): grid- and part-uniform
+      if (st[0] == PM_DONE) break;  // the pass mode: grid- and part-uniform
       if (!x.dev_ctl) each([&](uint32_t, Ctx& c) { part_lp_set(c, recs, minp); });
       if (!recs) continue;  // the next pass emits a window: it reads no records
       if (x.direct) exchange_lp_direct(cnt.data(), recs);

@@ -91,17 +91,10 @@ static void launch_pubsub(Ctx& c, const Batch& b) {
   hipStream_t s = c.stream;
   const unsigned grid = keys_pass_grid(c, ra.total);
   k_pubsub_pub<<<b.B, TB, 0, s>>>(ra, pa);
-#define GS_PUBSUB(FPV)                                                    \
-  k_pubsub_fwd<FPV><<<grid, TB, 0, s>>>(ra, pa);                          \
-  if (gossip && c.cfg.history_gossip) k_pubsub_gossip<FPV><<<grid, TB, 0, s>>>(ra, pa);
-  switch (b.FP) {
-    case 1: GS_PUBSUB(1) break;
-    case 2: GS_PUBSUB(2) break;
-    case 4: GS_PUBSUB(4) break;
-    case 8: GS_PUBSUB(8) break;
-    default: GS_PUBSUB(16) break;
-  }
-#undef GS_PUBSUB
+  with_fp(b.FP, [&](auto fp) {
+    k_pubsub_fwd<fp.value><<<grid, TB, 0, s>>>(ra, pa);
+    if (gossip && c.cfg.history_gossip) k_pubsub_gossip<fp.value><<<grid, TB, 0, s>>>(ra, pa);
+  });
   GS_HIP(hipGetLastError());
 }
 

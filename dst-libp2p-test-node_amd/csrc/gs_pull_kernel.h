@@ -42,8 +42,8 @@
 //   records > 0  -> PULL the window whose records were just emitted;
 //   else min < INF -> EMIT the window holding the min pending key (a gap);
 //   else DONE.
+// (PM_DONE / PM_EMIT / PM_PULL and the host's names of the slot words: gs_internal.h.)
 
-enum : uint64_t { PM_DONE = 0, PM_EMIT = 1, PM_PULL = 2 };
 constexpr uint32_t PULL_WAVES = TB / 64;  // rows in flight per block
 constexpr uint32_t PULL_LMAX = 1024;       // row lanes held in registers (16 chunks)
 constexpr uint32_t PULL_CH = PULL_LMAX / 64;
@@ -452,11 +452,5 @@ __global__ __launch_bounds__(TB) void k_srep(uint32_t N, uint32_t S, const uint3
 inline uint64_t pull_grain(uint32_t tshift) { return tshift >= 32 ? 1ull : 1ull << (32 - tshift); }
 
 void pull_dispatch(uint32_t FP, const PullArgs& a, unsigned grid, hipStream_t s) {
-  switch (FP) {
-    case 1: k_pull<1><<<grid, TB, 0, s>>>(a); break;
-    case 2: k_pull<2><<<grid, TB, 0, s>>>(a); break;
-    case 4: k_pull<4><<<grid, TB, 0, s>>>(a); break;
-    case 8: k_pull<8><<<grid, TB, 0, s>>>(a); break;
-    default: k_pull<16><<<grid, TB, 0, s>>>(a); break;
-  }
+  with_fp(FP, [&](auto fp) { k_pull<fp.value><<<grid, TB, 0, s>>>(a); });
 }

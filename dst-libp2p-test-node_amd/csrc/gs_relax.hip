@@ -562,17 +562,10 @@ static void run_complete(Ctx& c, const Batch& b, uint32_t u0, uint32_t un, bool 
   // tiles: 2048 blocks per tile, 595 us per batch, profiles/r04_v3)
   const uint64_t thick = (un + rows_per_block * 16 - 1) / (rows_per_block * 16);
   dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(thick, want)), tiles);
-#define GS_COMPLETE(FPV)                                                      \
-  if (hist) k_complete<FPV, true><<<grid, TB, 0, s>>>(ca);                    \
-  else k_complete<FPV, false><<<grid, TB, 0, s>>>(ca);
-  switch (b.FP) {
-    case 1: GS_COMPLETE(1) break;
-    case 2: GS_COMPLETE(2) break;
-    case 4: GS_COMPLETE(4) break;
-    case 8: GS_COMPLETE(8) break;
-    default: GS_COMPLETE(16) break;
-  }
-#undef GS_COMPLETE
+  with_fp(b.FP, [&](auto fp) {
+    if (hist) k_complete<fp.value, true><<<grid, TB, 0, s>>>(ca);
+    else k_complete<fp.value, false><<<grid, TB, 0, s>>>(ca);
+  });
   GS_HIP(hipGetLastError());
 }
 
@@ -932,17 +925,10 @@ static void launch_traffic(Ctx& c, const Batch& b) {
   hipStream_t s = c.stream;
   const unsigned grid = keys_pass_grid(c, ra.total);
   k_traffic_pub<<<b.B, TB, 0, s>>>(ra, ta);
-#define GS_TRAFFIC(FPV)                                                    \
-  k_traffic_fwd<FPV><<<grid, TB, 0, s>>>(ra, ta);                          \
-  if (gossip && c.cfg.history_gossip) k_traffic_gossip<FPV><<<grid, TB, 0, s>>>(ra, ta);
-  switch (b.FP) {
-    case 1: GS_TRAFFIC(1) break;
-    case 2: GS_TRAFFIC(2) break;
-    case 4: GS_TRAFFIC(4) break;
-    case 8: GS_TRAFFIC(8) break;
-    default: GS_TRAFFIC(16) break;
-  }
-#undef GS_TRAFFIC
+  with_fp(b.FP, [&](auto fp) {
+    k_traffic_fwd<fp.value><<<grid, TB, 0, s>>>(ra, ta);
+    if (gossip && c.cfg.history_gossip) k_traffic_gossip<fp.value><<<grid, TB, 0, s>>>(ra, ta);
+  });
   GS_HIP(hipGetLastError());
 }
 
@@ -985,6 +971,34 @@ static void timed_pass(Ctx& c, hipStream_t s, Fn&& launch) {
   c.ev_n += 3;
 }
 
+// The reverse positions of the mesh (k_rpos), once per mesh: every pull and list pass reads them.
+static void ensure_rpos(Ctx& c) {
+  if (c.rpos_valid) return;
+  const uint32_t N = c.cfg.peers;
+  hipStream_t s = c.stream;
+  c.d_rpos.alloc((size_t)N * MESH_W);
+  GS_HIP(hipMemsetAsync(c.d_counters.p + C_ERR, 0, 8, s));
+  k_rpos<<<(unsigned)(((uint64_t)N * MESH_W + TB - 1) / TB), TB, 0, s>>>(c.d_mesh.p, c.d_rpos.p, N, c.d_counters.p);
+  GS_HIP(hipGetLastError());
+  if (read_counter(c, C_ERR) & ERR_MESH) c.fail(GS_ERANGE, "mesh is not symmetric");
+  c.rpos_valid = true;
+}
+
+// The pass control before a batch's seeds: every slot {lo 0, DONE, 0 records, min INF}; the
+// batch words behind the slots (a no-log list pass's latest final time and deliveries) 0.
+static void pctrl_reset(Ctx& c) {
+  static_assert(LP_CT_TMAX == PS_SLOTS * PS_WORDS && PM_DONE == 0, "the batch words follow the slots; zero is DONE");
+  hipStream_t s = c.stream;
+  c.d_pctrl.alloc(LP_CT_WORDS);
+  GS_HIP(hipMemsetAsync(c.d_pctrl.p, 0, LP_CT_WORDS * 8, s));
+  for (uint32_t q = 0; q < PS_SLOTS; q++) GS_HIP(hipMemsetAsync(c.d_pctrl.p + q * PS_WORDS + PS_MIN, 0xFF, 8, s));
+}
+
+// In the host's last read of the control slots (h_pinned[0 ..]): the slot the last of `pass` passes wrote.
+static const uint64_t* last_slot(const Ctx& c, uint32_t pass) {
+  return c.h_pinned + ((pass - 1) % PS_SLOTS) * PS_WORDS;
+}
+
 // One batch on the owner-computes path (gs_pull_kernel.h): seed, then passes in
 // chunks of 8 until a pass decides DONE (one host read of the ctrl slots per chunk).
 static void run_pull_batch(Ctx& c, const Batch& b) {
@@ -994,19 +1008,10 @@ static void run_pull_batch(Ctx& c, const Batch& b) {
   c.d_chunkmin.alloc((size_t)N * PULL_CH);
   c.d_lrec.alloc(2 * NL);
   c.d_lcnt.alloc(2 * (size_t)N);
-  c.d_pctrl.alloc(12);
-  if (!c.rpos_valid) {
-    c.d_rpos.alloc((size_t)N * MESH_W);
-    GS_HIP(hipMemsetAsync(c.d_counters.p + C_ERR, 0, 8, s));
-    k_rpos<<<(unsigned)(((uint64_t)N * MESH_W + TB - 1) / TB), TB, 0, s>>>(c.d_mesh.p, c.d_rpos.p, N, c.d_counters.p);
-    GS_HIP(hipGetLastError());
-    if (read_counter(c, C_ERR) & ERR_MESH) c.fail(GS_ERANGE, "mesh is not symmetric");
-    c.rpos_valid = true;
-  }
+  ensure_rpos(c);
   GS_HIP(hipMemsetAsync(c.d_chunkmin.p, 0xFF, (size_t)N * PULL_CH * 4, s));
-  GS_HIP(hipMemsetAsync(c.d_pctrl.p, 0, 12 * 8, s));  // every slot {lo 0, DONE, 0 records, min INF}
-  for (int q = 0; q < 3; q++) GS_HIP(hipMemsetAsync(c.d_pctrl.p + q * 4 + 3, 0xFF, 8, s));
-  launch_seed(c, b, 0, N, c.d_pctrl.p + 2 * 4 + 3, c.d_chunkmin.p);
+  pctrl_reset(c);
+  launch_seed(c, b, 0, N, c.d_pctrl.p + PS_SEED_MIN, c.d_chunkmin.p);
   PullArgs pa{};
   pa.keys = c.d_keys.p; pa.busy = c.d_busy.p; pa.chunkmin = c.d_chunkmin.p;
   pa.lrec = c.d_lrec.p; pa.lcnt = c.d_lcnt.p; pa.rpos = c.d_rpos.p;
@@ -1026,9 +1031,9 @@ static void run_pull_batch(Ctx& c, const Batch& b) {
       timed_pass(c, s, [&] { pull_dispatch(b.FP, pa, grid, s); });
     }
     GS_HIP(hipGetLastError());
-    GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_pctrl.p, 12 * 8, hipMemcpyDeviceToHost, s));
+    GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_pctrl.p, PS_SLOTS * PS_WORDS * 8, hipMemcpyDeviceToHost, s));
     GS_HIP(hipStreamSynchronize(s));
-    if (c.h_pinned[((pass - 1) % 3) * 4 + 1] == PM_DONE) break;
+    if (last_slot(c, pass)[PS_MODE] == PM_DONE) break;
   }
   c.stats.relax_launches += pass;
 }
@@ -1141,9 +1146,11 @@ constexpr uint64_t NOLOG_TLIM = 1ull << 38;  // (t >> 6) / 15625 in 32 bits
 
 // What one list-pass batch runs with: dense rows for its reader (k_lfinal), IDONTWANT
 // (dense final keys all along), lazy gossip and churn inside the passes, batch slices,
-// the no-log form.
+// the no-log form. part: the rows are a part's (gs_part.h), row r is peer u0 + r and the pass
+// reads its neighbours' records from the packed exchange buffers (d_rpk, d_roffg, d_rcg).
 struct LpOpts {
-  bool dense = false, idw = false;
+  bool dense = false, idw = false, part = false;
+  uint32_t u0 = 0;
   const GosRun* gos = nullptr;
   const ChnRun* chn = nullptr;
   const Slices* sl = nullptr;
@@ -1165,10 +1172,11 @@ static unsigned lpull_grid(uint64_t rows, int cus) {
 
 // Test knobs, read per batch: GS_LPULL_CAP's small lists force the overflow re-run;
 // GS_LPULL_CAP_BATCHES (comma-separated 0-based indices of the run's batch loop, in run
-// order: after the class regrouping) keeps the cap to the listed batches
-static uint32_t lpull_cap(const Ctx& c, uint32_t ls) {
+// order: after the class regrouping) keeps the cap to the listed batches (by_batch: not for a
+// part, c.run_batch is gs_run's)
+static uint32_t lpull_cap(const Ctx& c, uint32_t ls, bool by_batch) {
   long cap = env_int("GS_LPULL_CAP", (long)ls);
-  const char* capb = getenv("GS_LPULL_CAP_BATCHES");
+  const char* capb = by_batch ? getenv("GS_LPULL_CAP_BATCHES") : nullptr;
   if (capb && *capb) {
     bool listed = false;
     for (const char* q = capb; *q && !listed;) {
@@ -1183,28 +1191,27 @@ static uint32_t lpull_cap(const Ctx& c, uint32_t ls) {
   return (uint32_t)std::min<long>(std::max(1l, cap), (long)ls);
 }
 
-// The batch's buffers, cleared state and saved counters, then its seeds: one entry per
-// (target, fragment) of every publish (flood: every connection), scap at the most.
-static void lpull_begin(Ctx& c, const Batch& b, uint32_t K, const LpOpts& o, uint32_t N, uint64_t scap) {
+// The seed list's entries at the most: one per (target, fragment) of every publish (flood: every connection).
+static uint64_t lpull_scap(const Ctx& c, const Batch& b, const LpOpts& o) {
+  return (uint64_t)(o.sl ? o.sl->S : 1) * b.B * b.Fe * std::max<uint64_t>(c.max_degree, MESH_W);
+}
+
+// The batch's buffers for the pass's N rows, cleared state and saved counters, then its seeds.
+// Both drivers' set-up: run_lpull_batch's for the whole graph (or its slices), part_lp_begin's
+// (gs_part.h) for a part's rows.
+static void lpull_begin(Ctx& c, const Batch& b, uint32_t K, const LpOpts& o, uint32_t N) {
   const uint32_t N0 = c.cfg.peers;
   const Slices* sl = o.sl;
   hipStream_t s = c.stream;
   const size_t NL = (size_t)N * b.L;
+  const uint64_t scap = lpull_scap(c, b, o);
   c.d_lrec.alloc((o.chn ? 4 : 2) * NL);  // churn records are 16 B
   c.d_lcnt.alloc(2 * (size_t)N);
-  c.d_pctrl.alloc(LP_CT_WORDS);
   c.d_lblk.alloc((size_t)K * N * lpull_stride(b));
   c.d_lst.alloc((size_t)N * LP_SW);
   c.d_lfin.alloc((size_t)N * LP_FW);
   if (!(o.nl && o.nl->on)) c.d_flane.alloc(NL);
-  if (!c.rpos_valid) {
-    c.d_rpos.alloc((size_t)N0 * MESH_W);
-    GS_HIP(hipMemsetAsync(c.d_counters.p + C_ERR, 0, 8, s));
-    k_rpos<<<(unsigned)(((uint64_t)N0 * MESH_W + TB - 1) / TB), TB, 0, s>>>(c.d_mesh.p, c.d_rpos.p, N0, c.d_counters.p);
-    GS_HIP(hipGetLastError());
-    if (read_counter(c, C_ERR) & ERR_MESH) c.fail(GS_ERANGE, "mesh is not symmetric");
-    c.rpos_valid = true;
-  }
+  ensure_rpos(c);
   if (sl) {  // the graph copies of the slices (rebuilt per group: a few MB)
     c.d_smesh.alloc((size_t)N * MESH_W);
     c.d_srpos.alloc((size_t)N * MESH_W);
@@ -1215,9 +1222,7 @@ static void lpull_begin(Ctx& c, const Batch& b, uint32_t K, const LpOpts& o, uin
   }
   GS_HIP(hipMemsetAsync(c.d_lst.p, 0, (size_t)N * LP_SW * 4, s));
   GS_HIP(hipMemsetAsync(c.d_lfin.p, 0, (size_t)N * LP_FW * 4, s));
-  // every slot {lo 0, DONE, 0 records, min INF}; the batch's latest final time and deliveries 0
-  GS_HIP(hipMemsetAsync(c.d_pctrl.p, 0, LP_CT_WORDS * 8, s));
-  for (int q = 0; q < 3; q++) GS_HIP(hipMemsetAsync(c.d_pctrl.p + q * 4 + 3, 0xFF, 8, s));
+  pctrl_reset(c);
   c.d_lp_save.alloc(C_COUNT);
   GS_HIP(hipMemcpyAsync(c.d_lp_save.p, c.d_counters.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
   c.d_skey.alloc(scap);
@@ -1226,9 +1231,9 @@ static void lpull_begin(Ctx& c, const Batch& b, uint32_t K, const LpOpts& o, uin
   GS_HIP(hipMemsetAsync(c.d_scnt.p, 0, 4, s));
   if (sl)
     for (uint32_t j = 0; j < sl->S; j++)
-      launch_seed(c, b, 0, N0, c.d_pctrl.p + 2 * 4 + 3, nullptr, true, sl->lpub + (size_t)j * b.B, j * N0);
+      launch_seed(c, b, 0, N0, c.d_pctrl.p + PS_SEED_MIN, nullptr, true, sl->lpub + (size_t)j * b.B, j * N0);
   else
-    launch_seed(c, b, 0, N, c.d_pctrl.p + 2 * 4 + 3, nullptr, true);
+    launch_seed(c, b, o.u0, N, c.d_pctrl.p + PS_SEED_MIN, nullptr, true);
 }
 
 // The passes' arguments but for lazy gossip's (lpull_gos_args); churn: its per-row state, cleared.
@@ -1256,6 +1261,8 @@ static LPullArgs lpull_args(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, con
   la.K = K; la.lb = lb; la.dG = (uint32_t)(la.delta / grain);
   la.idw = o.idw ? 1u : 0u;
   la.rmax = lpull_rmax(b);
+  la.u0 = o.u0;
+  if (o.part) la.rpk = c.d_rpk.p, la.roff = c.d_roffg.p, la.rcg = c.d_rcg.p;
   la.ghk = ~0u;
   la.gsw = ~0u;  // (frozen mesh: every heartbeat's IHAVEs are decided by the receivers)
   if (chn) {  // churn (gs_cpull.h): the tables k_cprep built for this batch
@@ -1291,8 +1298,30 @@ static LPullArgs lpull_args(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, con
     la.gsw = (uint32_t)env_int("GS_GOSSIP_SWITCH", ~0u);
   }
   la.ls = lpull_stride(b);
-  la.lcap = lpull_cap(c, la.ls);
+  la.lcap = lpull_cap(c, la.ls, !o.part);
   return la;
+}
+
+// The seeds into the candidate lists (k_lseed), the rows whose emit step needs the publishers
+// (k_lpubnb sets LP_PUB; not for a part, whose rows that kernel would index by global peer id:
+// it runs with pubw = 0) and the publishers' own lanes into the logs (k_lpub).
+static void lpull_seed(Ctx& c, const Batch& b, const LpOpts& o, LPullArgs& la) {
+  const Slices* sl = o.sl;
+  hipStream_t s = c.stream;
+  const uint64_t scap = lpull_scap(c, b, o);
+  k_lseed<<<(unsigned)std::max<uint64_t>(1, std::min<uint64_t>((scap + TB - 1) / TB, (uint64_t)c.num_cus * 4)), TB, 0, s>>>(
+      la, c.d_skey.p, c.d_slane.p, c.d_scnt.p);
+  if (!o.part) {
+    la.pubw = 1;
+    const uint64_t nm = (uint64_t)(sl ? sl->S : 1u) * b.B, width = (o.chn ? CELL_W : MESH_W) + 1;
+    k_lpubnb<<<(unsigned)((nm * width + TB - 1) / TB), TB, 0, s>>>(la, (uint32_t)nm);
+  }
+  for (uint32_t j = 0; j < (sl ? sl->S : 1u); j++) {  // (a slice's publishers are its rows)
+    LPullArgs lj = la;
+    if (sl) lj.pub = sl->spub + (size_t)j * b.B;
+    k_lpub<<<(b.B * b.Fe + 255) / 256, 256, 0, s>>>(lj, b.Fe);
+  }
+  GS_HIP(hipGetLastError());
 }
 
 // GOS: sender planes, row-done bits, heartbeat control (gs_lpull_kernel.h)
@@ -1333,7 +1362,7 @@ static void lpull_gos_args(Ctx& c, const Batch& b, const LpOpts& o, LPullArgs& l
 
 // Passes in groups of 8 until one decides DONE (one host read of the control slots, the
 // error word and, no-log, the batch words per group) or a list is lost. Returns the
-// passes run; c.h_pinned holds the last read.
+// passes run; c.h_pinned[HP_LP_ERR] and [HP_LP_BATCH ..] hold the last read of those.
 static uint32_t lpull_passes(Ctx& c, uint32_t FP, LPullArgs& la, unsigned grid, bool gos, bool nolog) {
   hipStream_t s = c.stream;
   uint32_t pass = 0;
@@ -1343,23 +1372,23 @@ static uint32_t lpull_passes(Ctx& c, uint32_t FP, LPullArgs& la, unsigned grid, 
       timed_pass(c, s, [&] { lpull_dispatch(FP, la, grid, s, gos, nolog); });
     }
     GS_HIP(hipGetLastError());
-    GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_pctrl.p, 12 * 8, hipMemcpyDeviceToHost, s));
-    GS_HIP(hipMemcpyAsync(c.h_pinned + 12, c.d_counters.p + C_ERR, 8, hipMemcpyDeviceToHost, s));  // same sync
+    GS_HIP(hipMemcpyAsync(c.h_pinned, c.d_pctrl.p, PS_SLOTS * PS_WORDS * 8, hipMemcpyDeviceToHost, s));
+    GS_HIP(hipMemcpyAsync(c.h_pinned + HP_LP_ERR, c.d_counters.p + C_ERR, 8, hipMemcpyDeviceToHost, s));  // same sync
     if (nolog)  // (and the batch words: final once DONE is read)
-      GS_HIP(hipMemcpyAsync(c.h_pinned + 13, c.d_pctrl.p + LP_CT_TMAX, 16, hipMemcpyDeviceToHost, s));
+      GS_HIP(hipMemcpyAsync(c.h_pinned + HP_LP_BATCH, c.d_pctrl.p + LP_CT_TMAX, 16, hipMemcpyDeviceToHost, s));
     if (c.pass_poll) c.pass_poll();  // (while these passes run: the next batch's epoch chain is enqueued)
     GS_HIP(hipStreamSynchronize(s));
+    const uint64_t* sl = last_slot(c, pass);
     static const bool dbg_pass = getenv("GS_DEBUG_PASSES") != nullptr;
     if (dbg_pass && pass % 256 == 0)
       fprintf(stderr, "[gs] pass %u: mode %llu lo %llu records %llu min %llx err %llx\n", pass,
-              (unsigned long long)c.h_pinned[((pass - 1) % 3) * 4 + 1], (unsigned long long)c.h_pinned[((pass - 1) % 3) * 4],
-              (unsigned long long)c.h_pinned[((pass - 1) % 3) * 4 + 2],
-              (unsigned long long)c.h_pinned[((pass - 1) % 3) * 4 + 3], (unsigned long long)c.h_pinned[12]);
+              (unsigned long long)sl[PS_MODE], (unsigned long long)sl[PS_LO], (unsigned long long)sl[PS_RECORDS],
+              (unsigned long long)sl[PS_MIN], (unsigned long long)c.h_pinned[HP_LP_ERR]);
     // a batch's passes end (every window of its lifetime emitted); a count far
     // past that is a bug, reported instead of looping
     if (pass > (1u << 20)) c.fail(GS_ERANGE, "internal: the list pass did not finish in 2^20 passes");
-    if (c.h_pinned[((pass - 1) % 3) * 4 + 1] == PM_DONE) break;
-    if (c.h_pinned[12] & (ERR_LIST | ERR_RING)) break;  // lost already: stop early, re-run on k_pull
+    if (sl[PS_MODE] == PM_DONE) break;
+    if (c.h_pinned[HP_LP_ERR] & (ERR_LIST | ERR_RING)) break;  // lost already: stop early, re-run on k_pull
   }
   return pass;
 }
@@ -1379,32 +1408,20 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, con
   const bool nolog = nl && nl->on;
   if (nolog && (o.dense || o.idw || o.gos || o.chn || sl || b.FP != 1))
     c.fail(GS_EINVAL, "internal: no-log list pass asked for a batch it cannot take");
-  const uint64_t scap = (uint64_t)(sl ? sl->S : 1) * b.B * b.Fe * std::max<uint64_t>(c.max_degree, MESH_W);
-  lpull_begin(c, b, K, o, N, scap);
+  lpull_begin(c, b, K, o, N);
   LPullArgs la = lpull_args(c, b, K, lb, o, N);
   const unsigned grid = lpull_grid(N, c.num_cus);
-  k_lseed<<<(unsigned)std::max<uint64_t>(1, std::min<uint64_t>((scap + TB - 1) / TB, (uint64_t)c.num_cus * 4)), TB, 0, s>>>(
-      la, c.d_skey.p, c.d_slane.p, c.d_scnt.p);
-  {  // the rows whose emit step needs the publishers (LP_PUB)
-    la.pubw = 1;
-    const uint64_t nm = (uint64_t)(sl ? sl->S : 1u) * b.B, width = (o.chn ? CELL_W : MESH_W) + 1;
-    k_lpubnb<<<(unsigned)((nm * width + TB - 1) / TB), TB, 0, s>>>(la, (uint32_t)nm);
-  }
-  for (uint32_t j = 0; j < (sl ? sl->S : 1u); j++) {  // (a slice's publishers are its rows)
-    LPullArgs lj = la;
-    if (sl) lj.pub = sl->spub + (size_t)j * b.B;
-    k_lpub<<<(b.B * b.Fe + 255) / 256, 256, 0, s>>>(lj, b.Fe);
-  }
-  GS_HIP(hipGetLastError());
+  lpull_seed(c, b, o, la);
   if (o.gos) lpull_gos_args(c, b, o, la);
   c.stats.relax_launches += lpull_passes(c, b.FP, la, grid, o.gos != nullptr, nolog);
-  if (c.h_pinned[12] & (ERR_LIST | ERR_RING)) {  // the error word as of the last pass read
+  if (c.h_pinned[HP_LP_ERR] & (ERR_LIST | ERR_RING)) {  // the error word as of the last pass read
     GS_HIP(hipMemcpyAsync(c.d_counters.p, c.d_lp_save.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
     return false;
   }
-  static_assert(LP_CT_DELIV == LP_CT_TMAX + 1 && 13 + 2 <= H_PINNED_WORDS, "the batch words' host copy");
+  static_assert(LP_CT_DELIV == LP_CT_TMAX + 1, "the batch words' host copy");
+  const uint64_t* bw = c.h_pinned + HP_LP_BATCH;  // LP_CT_TMAX, LP_CT_DELIV as of the last pass read
   static const bool dbg_comp = getenv("GS_DEBUG_COMPLETION") != nullptr;
-  if (nolog && c.h_pinned[13] >= NOLOG_TLIM) {  // the in-pass ms were not exact: restored as after an overflow
+  if (nolog && bw[0] >= NOLOG_TLIM) {  // the in-pass ms were not exact: restored as after an overflow
     GS_HIP(hipMemcpyAsync(c.d_counters.p, c.d_lp_save.p, C_COUNT * 8, hipMemcpyDeviceToDevice, s));
     nl->inexact = true;
     if (dbg_comp)
@@ -1417,8 +1434,8 @@ static bool run_lpull_batch(Ctx& c, const Batch& b, uint32_t K, uint32_t lb, con
     fprintf(stderr, "[lp] batch %llu: completion %s\n", (unsigned long long)c.run_batch,
             nolog ? "in-pass (no log)" : o.idw ? "dense keys (idontwant)" : o.dense ? "dense rows (k_lfinal)" : "final log");
   if (nolog) {  // nothing to complete: no log was written, the counters are added
-    nl->tmax = c.h_pinned[13];
-    nl->deliv = c.h_pinned[14];
+    nl->tmax = bw[0];
+    nl->deliv = bw[1];
     c.keys_none = true;
     return true;
   }

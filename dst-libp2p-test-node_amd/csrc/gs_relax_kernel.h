@@ -1069,11 +1069,5 @@ void relax_fp(PushForm f, const RelaxArgs& a, unsigned grid, hipStream_t s, hipE
 
 void relax_dispatch(uint32_t FP, PushForm f, const RelaxArgs& a, unsigned grid, hipStream_t s,
                     hipEvent_t mid = nullptr) {
-  switch (FP) {
-    case 1: relax_fp<1>(f, a, grid, s, mid); break;
-    case 2: relax_fp<2>(f, a, grid, s, mid); break;
-    case 4: relax_fp<4>(f, a, grid, s, mid); break;
-    case 8: relax_fp<8>(f, a, grid, s, mid); break;
-    default: relax_fp<16>(f, a, grid, s, mid); break;
-  }
+  with_fp(FP, [&](auto fp) { relax_fp<fp.value>(f, a, grid, s, mid); });
 }

@@ -405,3 +405,58 @@ def test_run_partitioned_refuses_traffic():
     with pytest.raises(gossipsim.GossipSimError, match="GS_EUNSUPPORTED"):
         comm.run_partitioned(sims, _sched(4, 600))
     comm.close()
+
+
+@pytest.mark.parametrize("fragments", [1, 2])
+def test_one_context_takes_whole_and_partitioned_batches_in_turn(monkeypatch, fragments):
+    """The two list-pass drivers share one set-up and the context's buffers (pass
+    control, records, counts, candidate lists, final bits and lanes, reverse
+    positions, seed list). Two contexts that hold the halves of 1001 peers (500 and
+    501 rows) take, in turn: a partitioned batch; on part 0's context a whole-graph
+    batch that reads only counters (the no-log pass for fragments=1: the buffers
+    grow from 500 to 1001 rows, no final lanes); a whole-graph batch whose capped
+    lists send it to k_pull, on the same control and record buffers; a partitioned
+    batch again, rows of 500 in buffers sized for 1001; a whole-graph batch on part
+    1's context. Every step's rows and summed counters equal the oracle's."""
+    N, M, S, links = 1001, 24, 5, (50, 150, 40, 130)
+    p = oracle.params(peers=N, seed=67, fragments=fragments)
+    assert p.lazy_gossip  # both drivers run the no-op proof
+    sched = _sched(M, N)
+    ref = oracle.simulate(p, S, links, sched=sched)
+    sims = _parts(p, S, links, 2, M)
+    comm = gossipsim.Comm(local_parts=2)
+    counters = ("deliveries", "frag_deliveries", "relaxations", "bytes_alg", "latency_sum_ms")
+
+    def exact(rows, stats):
+        if rows is not None:
+            np.testing.assert_array_equal(np.concatenate([r["t_complete"] for r in rows], axis=1), ref["t_complete"])
+            np.testing.assert_array_equal(np.concatenate([r["hops"] for r in rows], axis=1), ref["hops"])
+        for k in counters:
+            assert sum(x[k] for x in stats) == ref["stats"][k], k
+        assert max(x["latency_max_ms"] for x in stats) == ref["stats"]["latency_max_ms"]
+        assert all(x["messages"] == M for x in stats)
+
+    def partitioned():
+        for s in sims:
+            s.reset_stats()
+        rows = comm.run_partitioned(sims, sched)
+        st = [s.stats() for s in sims]
+        exact(rows, st)
+        assert all(x["list_pull_batches"] > 0 for x in st)
+
+    def whole(sim, **kw):
+        sim.reset_stats()
+        res = sim.run(sched, **kw)
+        st = sim.stats()
+        exact([res] if "t_complete" in res else None, [st])
+        return st
+
+    partitioned()
+    assert whole(sims[0], collect=False)["list_pull_batches"] > 0
+    monkeypatch.setenv("GS_LPULL_CAP", "2")
+    assert whole(sims[0])["list_pull_batches"] == 0
+    monkeypatch.delenv("GS_LPULL_CAP")
+    partitioned()
+    st = whole(sims[1])
+    assert st["list_pull_batches"] == st["batches"] > 0
+    comm.close()
