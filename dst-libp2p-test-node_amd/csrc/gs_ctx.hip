@@ -385,6 +385,46 @@ extern "C" gs_status gs_reset_pubsub_counts(gs_ctx* ctx) {
   GS_API_END(ctx)
 }
 
+// ---- mesh events and per-epoch mesh health of the last converge (gs_meshev.h) ----
+extern "C" gs_status gs_set_mesh_events(gs_ctx* ctx, uint32_t enable) {
+  GS_API_BEGIN(ctx)
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  mesh_events_set(*ctx, enable != 0);
+  GS_API_END(ctx)
+}
+
+static void mesh_events_ready(gs_ctx* ctx) {
+  if (!ctx->meshev) ctx->fail(GS_ESTATE, "gs_set_mesh_events(ctx, 1) first");
+  if (!ctx->meshev_valid) ctx->fail(GS_ESTATE, "gs_mesh_converge after gs_set_mesh_events(ctx, 1) first");
+}
+
+extern "C" gs_status gs_get_mesh_events(gs_ctx* ctx, uint64_t* out) {
+  GS_API_BEGIN(ctx)
+  if (!out) ctx->fail(GS_EINVAL, "null mesh events array");
+  mesh_events_ready(ctx);
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  mesh_events_get(*ctx, out);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_mesh_series_rows(gs_ctx* ctx, uint32_t* rows) {
+  GS_API_BEGIN(ctx)
+  if (!rows) ctx->fail(GS_EINVAL, "null rows");
+  mesh_events_ready(ctx);
+  *rows = (uint32_t)(ctx->me_series.size() / GS_MESH_SERIES_COLS);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_get_mesh_series(gs_ctx* ctx, uint64_t* out, uint32_t rows) {
+  GS_API_BEGIN(ctx)
+  if (!out) ctx->fail(GS_EINVAL, "null mesh series array");
+  mesh_events_ready(ctx);
+  if ((size_t)rows * GS_MESH_SERIES_COLS != ctx->me_series.size())
+    ctx->fail(GS_EINVAL, "gs_get_mesh_series: rows is not gs_mesh_series_rows' count");
+  std::copy(ctx->me_series.begin(), ctx->me_series.end(), out);
+  GS_API_END(ctx)
+}
+
 // ---- per-peer delay accumulators (gs_peerdelay.h) ----
 extern "C" gs_status gs_set_peer_delay(gs_ctx* ctx, uint32_t enable) {
   GS_API_BEGIN(ctx)

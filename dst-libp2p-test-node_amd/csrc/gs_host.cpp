@@ -765,6 +765,61 @@ extern "C" gs_status gs_write_pubsub_metrics(const gs_config* cfg, const char* p
   return GS_OK;
 }
 
+// The go node's GRAFT / PRUNE / subscription counters (go-test-node/metrics.go:164-190,
+// 100-122) and its tracer's mesh gauges (metrics.go:224-258 the mesh size, 328-362 the topic
+// health: one topic, so each class is 0 or 1 per peer) from the per-peer mesh events
+// (gs_get_mesh_events), the CSR degree and the mesh size, in the Prometheus text format.
+extern "C" gs_status gs_write_mesh_metrics(const gs_config* cfg, const char* path, uint32_t peers,
+                                           const uint64_t* row_ptr, const uint8_t* mesh_count,
+                                           const uint64_t* events) {
+  if (!cfg || !path || !row_ptr || !mesh_count || !events) return GS_EINVAL;
+  FILE* f = fopen(path, "w");
+  if (!f) return GS_EINVAL;
+  std::vector<char> buf(1 << 20);
+  setvbuf(f, buf.data(), _IOFBF, buf.size());
+  auto family = [&](const char* name, const char* type, const char* help, bool topic, auto value) {
+    fprintf(f, "# HELP %s %s\n# TYPE %s %s\n", name, help, name, type);
+    for (uint32_t u = 0; u < peers; u++)
+      fprintf(f, "%s{%speer_id=\"pod-%u\"} %llu\n", name, topic ? "topic=\"test\"," : "", u,
+              (unsigned long long)value(u));
+  };
+  auto col = [&](int k) { return [=](uint32_t u) { return events[(size_t)u * GS_MESH_EVENT_COLS + k]; }; };
+  auto deg = [&](uint32_t u) { return row_ptr[u + 1] - row_ptr[u]; };
+  const uint32_t d_lo = cfg->d_lo;
+  family("libp2p_pubsub_broadcast_graft_total", "counter", "pubsub broadcast graft", true, col(GS_ME_GRAFT_TX));
+  family("libp2p_pubsub_received_graft_total", "counter", "pubsub received graft", true, col(GS_ME_GRAFT_RX));
+  family("libp2p_pubsub_broadcast_prune_total", "counter", "pubsub broadcast prune", true, col(GS_ME_PRUNE_TX));
+  family("libp2p_pubsub_received_prune_total", "counter", "pubsub received prune", true, col(GS_ME_PRUNE_RX));
+  family("libp2p_pubsub_broadcast_subscriptions_total", "counter", "pubsub broadcast subscriptions", true, deg);
+  family("libp2p_pubsub_received_subscriptions_total", "counter", "pubsub received subscriptions", true, deg);
+  family("libp2p_gossipsub_peers_per_topic_mesh", "gauge", "gossipsub peers per topic in mesh", true,
+         [&](uint32_t u) { return (uint64_t)mesh_count[u]; });
+  family("libp2p_gossipsub_low_peers_topics", "gauge", "number of topics in mesh with at least one but below dlow peers",
+         false, [&](uint32_t u) { return (uint64_t)(mesh_count[u] > 0 && mesh_count[u] < d_lo); });
+  family("libp2p_gossipsub_healthy_peers_topics", "gauge", "number of topics in mesh with at least dlow peers", false,
+         [&](uint32_t u) { return (uint64_t)(mesh_count[u] > 0 && mesh_count[u] >= d_lo); });
+  family("libp2p_gossipsub_no_peers_topics", "gauge", "number of topics in mesh with no peers", false,
+         [&](uint32_t u) { return (uint64_t)(mesh_count[u] == 0); });
+  if (fclose(f)) return GS_EINVAL;
+  return GS_OK;
+}
+
+// The per-epoch mesh health (gs_get_mesh_series) as CSV, one line per epoch.
+extern "C" gs_status gs_write_mesh_series(const char* path, const uint64_t* series, uint32_t rows) {
+  if (!path || !series) return GS_EINVAL;
+  FILE* f = fopen(path, "w");
+  if (!f) return GS_EINVAL;
+  fputs("epoch,online,no_peers,low,healthy,over,links,grafts,rejects,prunes,drops,adds,dels\n", f);
+  for (uint32_t h = 0; h < rows; h++) {
+    fprintf(f, "%u", h);
+    for (uint32_t k = 0; k < GS_MESH_SERIES_COLS; k++)
+      fprintf(f, ",%llu", (unsigned long long)series[(size_t)h * GS_MESH_SERIES_COLS + k]);
+    fputc('\n', f);
+  }
+  if (fclose(f)) return GS_EINVAL;
+  return GS_OK;
+}
+
 // shadow/run.sh:34-36 + shadow/README.md:76-78: publisher_id, rotation 0/1,
 // inter_message_delay. tx_time is the publish instant (main.rs:105-111).
 extern "C" gs_status gs_schedule_runsh(uint32_t n_msgs, uint32_t peers, uint32_t publisher_id,

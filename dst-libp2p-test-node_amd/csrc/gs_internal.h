@@ -157,6 +157,16 @@ struct Ctx {
   bool pdelay = false;
   DevBuf<uint64_t> d_pdelay;   // [PD_COLS][own rows]
   uint32_t pdelay_n = 0;       // the rows d_pdelay covers (0: zeroed at the next use, part_set after a new split)
+  // gs_set_mesh_events (gs_meshev.h): the mesh events of the last gs_mesh_converge, all N peers
+  bool meshev = false;
+  bool meshev_valid = false;          // a converge finished since the switch went on
+  DevBuf<uint64_t> d_me;              // [GS_MESH_EVENT_COLS][N] per-peer counts
+  DevBuf<uint32_t> d_me_size;         // [N] mesh size after the last counted epoch
+  DevBuf<uint64_t> d_ms;              // [me_cap][GS_MESH_SERIES_COLS] series rows of stepped epochs, in stepping order
+  uint32_t me_cap = 0, me_used = 0;   // its rows, and those written since the last read-back
+  std::vector<uint32_t> me_epochs;    // the epoch of every stepped row
+  std::vector<uint64_t> me_stepped;   // the stepped rows read back so far
+  std::vector<uint64_t> me_series;    // [out_epochs + 1][GS_MESH_SERIES_COLS]: every epoch's row (me_finish)
 
   // links
   uint32_t S = 0;
@@ -474,6 +484,9 @@ void log_text_reset(Ctx& c);
 void pubsub_set(Ctx& c, bool on);
 void pubsub_reset(Ctx& c);
 void pubsub_get(Ctx& c, uint64_t* out);
+// mesh event counts of the last converge (gs_meshev.h, gs_mesh.hip)
+void mesh_events_set(Ctx& c, bool on);
+void mesh_events_get(Ctx& c, uint64_t* out);
 void peer_delay_set(Ctx& c, bool on);
 void peer_delay_reset(Ctx& c);
 void peer_delay_get(Ctx& c, gs_peer_delay* out);

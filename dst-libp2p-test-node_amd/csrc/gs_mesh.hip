@@ -1052,6 +1052,8 @@ inline unsigned row_blocks(uint32_t N, uint32_t G) { return (unsigned)(((uint64_
     else kernel<64><<<row_blocks(N, 64), TB, 0, s>>>(__VA_ARGS__);                      \
   } while (0)
 
+#include "gs_meshev.h"
+
 // Inverse IHAVE lists of the ring snapshots: epochs per chunk (the masks of a
 // chunk take <= 256 MB of d_gout), one chunk [h0, h0 + ny) on stream s.
 static uint64_t ring_in_chunk_epochs(uint32_t N) {
@@ -1129,8 +1131,9 @@ MeshArgs mesh_args(Ctx& c, hipStream_t s = nullptr) {
 }
 
 // The subscription epoch 0 from the cleared mesh (everyone online; DESIGN.md
-// §2.3): handshake-ordered grafts, GRAFT handling, apply.
-void sub_epoch(Ctx& c, MeshArgs a) {
+// §2.3): handshake-ordered grafts, GRAFT handling, apply. `count`: a converge with
+// gs_set_mesh_events counts the epoch's events (gs_meshev.h).
+void sub_epoch(Ctx& c, MeshArgs a, bool count = false) {
   if (!c.cfg.sub_graft) return;
   const uint32_t N = c.cfg.peers;
   hipStream_t s = c.stream;
@@ -1141,15 +1144,16 @@ void sub_epoch(Ctx& c, MeshArgs a) {
   const uint32_t G = row_group(c);
   GS_ROWS(k_heartbeat, G, N, s, a);
   GS_ROWS(k_handle_graft, G, N, s, a);
+  if (count) me_epoch(c, a, G, s);
   GS_ROWS(k_apply, G, N, s, a);
   GS_HIP(hipGetLastError());
 }
 
 // Epoch h of a run [h0, h1] of event-driven epochs (three steps on stream s):
 // lin[y] = offline bitset of epoch h0 - 1 + y; `ring`: the slot h % ring_R gets
-// the mask ring row (and, `ell`, the ELL snapshot).
+// the mask ring row (and, `ell`, the ELL snapshot). `count`: as sub_epoch.
 static void ev_epoch(Ctx& c, MeshArgs& a, uint64_t h, uint64_t h0, uint64_t h1, const uint64_t* lin, uint32_t w64,
-                     bool ring, bool ell, uint32_t G, hipStream_t s) {
+                     bool ring, bool ell, uint32_t G, hipStream_t s, bool count = false) {
   const uint32_t N = c.cfg.peers;
   const unsigned sgrid = (unsigned)((N + 63) / 64);  // one scanning wave (64 rows) per block of the steps
 #define GS_EVS(STEP, ...)                                                          \
@@ -1176,14 +1180,15 @@ static void ev_epoch(Ctx& c, MeshArgs& a, uint64_t h, uint64_t h0, uint64_t h1, 
   an.mm_prev = nullptr;
   GS_EVS(EV_HB, an, nullptr, nullptr);
   GS_EVS(EV_GRAFT, an, nullptr, nullptr);
+  if (count) me_epoch(c, an, G, s);
   GS_EVS(EV_APPLY, a, mesh, prev);
 #undef GS_EVS
 }
 
 // Event-driven churn epochs [h0, h1] (see k_ev_step): offline bitsets
 // of [h0-1, h1] in one launch (and into the ring), three row steps per epoch,
-// then the IHAVE targets of every ring slot written.
-void ev_epochs(Ctx& c, MeshArgs a, uint64_t h0, uint64_t h1, bool ring) {
+// then the IHAVE targets of every ring slot written. `count`: as sub_epoch (run_mesh only).
+void ev_epochs(Ctx& c, MeshArgs a, uint64_t h0, uint64_t h1, bool ring, bool count = false) {
   const uint32_t N = c.cfg.peers;
   const uint32_t w64 = (N + 63) / 64;
   hipStream_t s = c.stream;
@@ -1241,7 +1246,7 @@ void ev_epochs(Ctx& c, MeshArgs a, uint64_t h0, uint64_t h1, bool ring) {
     GS_HIP(hipStreamWaitEvent(c.side, e, 0));
   }
   for (uint64_t h = h0; h <= h1; h++) {
-    ev_epoch(c, a, h, h0, h1, lin, w64, ring, ring && !(c.ring_ell_defer && c.d_ring_mm.p), G, s);
+    ev_epoch(c, a, h, h0, h1, lin, w64, ring, ring && !(c.ring_ell_defer && c.d_ring_mm.p), G, s, count);
     if (c.epoch_hook && ring) c.epoch_hook(h);
     if (lists && h >= hr && (h + 1 - chunk0 == CE || h == h1)) {
       const hipEvent_t e = side_event(c, nev++);
@@ -1517,11 +1522,15 @@ uint32_t run_mesh(Ctx& c, uint32_t max_hb) {
   c.ring_in_tag.assign(c.ring_in_tag.size(), ~0ull);  // a new mesh: the churn ring restarts
   c.ring_ell_tag.assign(c.ring_ell_tag.size(), ~0ull);
   c.glp_prefer = false;  // and gossip batches try the eager pass + no-op proof first again
-  sub_epoch(c, a);
+  // gs_set_mesh_events: the epochs this call steps are counted (not those gs_run's chain
+  // steps or replays later); under churn the device holds every epoch's series row
+  const bool count = c.meshev;
+  if (count) me_begin(c, c.cfg.churn_ppm ? (uint64_t)max_hb + 1 : std::min<uint64_t>((uint64_t)max_hb + 1, ME_CHUNK));
+  sub_epoch(c, a, count);
   uint32_t epoch = 1, last = 0;
   uint64_t* h = c.h_pinned;
   if (c.cfg.churn_ppm) {  // no fixed point under churn: exactly max_hb epochs
-    if (max_hb >= 1) ev_epochs(c, a, 1, max_hb, false);
+    if (max_hb >= 1) ev_epochs(c, a, 1, max_hb, false, count);
     last = max_hb;
     c.churn_state = max_hb;  // the ring restarts after this state
     c.ring_lo = (uint64_t)max_hb + 1;
@@ -1535,6 +1544,7 @@ uint32_t run_mesh(Ctx& c, uint32_t max_hb) {
     const uint32_t G = row_group(c);
     GS_ROWS(k_heartbeat, G, N, s, a);
     GS_ROWS(k_handle_graft, G, N, s, a);
+    if (count) me_epoch(c, a, G, s);
     GS_ROWS(k_apply, G, N, s, a);
     GS_HIP(hipGetLastError());
     GS_HIP(hipMemcpyAsync(h, c.d_counters.p + C_MESH_CHANGES, 8, hipMemcpyDeviceToHost, s));
@@ -1557,7 +1567,31 @@ uint32_t run_mesh(Ctx& c, uint32_t max_hb) {
   GS_HIP(hipMemcpyAsync(h, c.d_counters.p + C_ERR, 8, hipMemcpyDeviceToHost, s));
   GS_HIP(hipStreamSynchronize(s));
   if (h[0] & ERR_MESH) c.fail(GS_ERANGE, "mesh row exceeds GS_MESH_W entries");
+  if (count) {
+    me_finish(c, last);
+    c.meshev_valid = true;
+  }
   return last;
+}
+
+// gs_set_mesh_events: the results exist from the next converge on.
+void mesh_events_set(Ctx& c, bool on) {
+  c.meshev = false;
+  c.meshev_valid = false;
+  if (!on) return;
+  c.d_me.alloc((size_t)c.cfg.peers * GS_MESH_EVENT_COLS);
+  c.d_me_size.alloc(c.cfg.peers);
+  c.meshev = true;
+}
+
+// gs_get_mesh_events: the columns [col][N] out as out[N][col].
+void mesh_events_get(Ctx& c, uint64_t* out) {
+  const size_t N = c.cfg.peers;
+  std::vector<uint64_t> h(N * GS_MESH_EVENT_COLS);
+  GS_HIP(hipMemcpyAsync(h.data(), c.d_me.p, h.size() * 8, hipMemcpyDeviceToHost, c.stream));
+  GS_HIP(hipStreamSynchronize(c.stream));
+  for (size_t u = 0; u < N; u++)
+    for (size_t k = 0; k < GS_MESH_EVENT_COLS; k++) out[u * GS_MESH_EVENT_COLS + k] = h[k * N + u];
 }
 
 }  // namespace gs

@@ -137,6 +137,12 @@ SIGNATURES = {
     "gs_get_pubsub_counts": (i32, [ctypes.c_void_p, P(u64)]),
     "gs_reset_pubsub_counts": (i32, [ctypes.c_void_p]),
     "gs_write_pubsub_metrics": (i32, [P(GsConfig), ctypes.c_char_p, u32, P(u64)]),
+    "gs_set_mesh_events": (i32, [ctypes.c_void_p, u32]),
+    "gs_get_mesh_events": (i32, [ctypes.c_void_p, P(u64)]),
+    "gs_mesh_series_rows": (i32, [ctypes.c_void_p, P(u32)]),
+    "gs_get_mesh_series": (i32, [ctypes.c_void_p, P(u64), u32]),
+    "gs_write_mesh_metrics": (i32, [P(GsConfig), ctypes.c_char_p, u32, P(u64), P(u8), P(u64)]),
+    "gs_write_mesh_series": (i32, [ctypes.c_char_p, P(u64), u32]),
     "gs_set_peer_delay": (i32, [ctypes.c_void_p, u32]),
     "gs_get_peer_delay": (i32, [ctypes.c_void_p, P(GsPeerDelay)]),
     "gs_reset_peer_delay": (i32, [ctypes.c_void_p]),
@@ -288,6 +294,40 @@ def write_pubsub_metrics(cfg, path, counts):
     rc = lib().gs_write_pubsub_metrics(ctypes.byref(cfg.c), path.encode(), pc.shape[0], _ptr(pc, u64))
     if rc:
         raise GossipSimError(rc, "gs_write_pubsub_metrics failed")
+
+
+# gs_get_mesh_events columns (GS_ME_*) and gs_get_mesh_series columns (GS_MS_*)
+MESH_EVENT_COLS = ("tx_graft", "rx_graft", "tx_prune", "rx_prune", "mesh_add", "mesh_del", "mesh_drop")
+MESH_SERIES_COLS = ("online", "no_peers", "low", "healthy", "over", "links", "grafts", "rejects", "prunes", "drops",
+                    "adds", "dels")
+
+
+def write_mesh_metrics(cfg, path, row_ptr, mesh_count, events):
+    """Prometheus text of the go node's GRAFT / PRUNE / subscription counters and mesh gauges
+    (go-test-node/metrics.go:164-190, 224-258, 328-362) for every peer (gs_write_mesh_metrics).
+    events: uint64 [peers, len(MESH_EVENT_COLS)] (Simulator.mesh_events)."""
+    ev = np.ascontiguousarray(events, np.uint64)
+    if ev.ndim != 2 or ev.shape[1] != len(MESH_EVENT_COLS):
+        raise GossipSimError(GS_EINVAL, "events [peers, %d] are needed" % len(MESH_EVENT_COLS))
+    row = np.ascontiguousarray(row_ptr, np.uint64)
+    mc = np.ascontiguousarray(mesh_count, np.uint8)
+    if row.shape != (ev.shape[0] + 1,) or mc.shape != (ev.shape[0],):
+        raise GossipSimError(GS_EINVAL, "row_ptr [peers + 1] and mesh_count [peers] are needed")
+    rc = lib().gs_write_mesh_metrics(ctypes.byref(cfg.c), path.encode(), ev.shape[0], _ptr(row, u64), _ptr(mc, u8),
+                                     _ptr(ev, u64))
+    if rc:
+        raise GossipSimError(rc, "gs_write_mesh_metrics failed")
+
+
+def write_mesh_series(path, series):
+    """The per-epoch mesh health as CSV (gs_write_mesh_series). series: uint64
+    [rows, len(MESH_SERIES_COLS)] (Simulator.mesh_series)."""
+    se = np.ascontiguousarray(series, np.uint64)
+    if se.ndim != 2 or se.shape[1] != len(MESH_SERIES_COLS):
+        raise GossipSimError(GS_EINVAL, "series [rows, %d] are needed" % len(MESH_SERIES_COLS))
+    rc = lib().gs_write_mesh_series(path.encode(), _ptr(se, u64), se.shape[0])
+    if rc:
+        raise GossipSimError(rc, "gs_write_mesh_series failed")
 
 
 def write_testnode_metrics(cfg, path, row_ptr, mesh_count, schedule, delay):
@@ -712,6 +752,35 @@ class Simulator:
     def write_node_metrics(self, path):
         """Every peer's Prometheus metrics (rust-test-node/src/metrics.rs names) after traffic runs."""
         write_node_metrics(self.cfg, path, self.csr()[0], self.mesh()[1], self.traffic())
+
+    # ---- mesh events and per-epoch mesh health (gs_set_mesh_events, DESIGN.md §2.15) ----
+    def set_mesh_events(self, on=True):
+        """While on, every mesh_converge records the per-peer GRAFT / PRUNE / mesh event counts and
+        one row of network-wide mesh health per epoch it steps (the later epochs of run's churn
+        chain are not counted)."""
+        self._check(lib().gs_set_mesh_events(self.ctx, 1 if on else 0))
+
+    def mesh_events(self):
+        """-> uint64 [N, len(MESH_EVENT_COLS)] of the last mesh_converge, in MESH_EVENT_COLS order."""
+        ev = np.zeros((self.peers, len(MESH_EVENT_COLS)), np.uint64)
+        self._check(lib().gs_get_mesh_events(self.ctx, _ptr(ev, u64)))
+        return ev
+
+    def mesh_series(self):
+        """-> uint64 [epochs + 1, len(MESH_SERIES_COLS)]: row h is the mesh after epoch h."""
+        rows = u32()
+        self._check(lib().gs_mesh_series_rows(self.ctx, ctypes.byref(rows)))
+        se = np.zeros((rows.value, len(MESH_SERIES_COLS)), np.uint64)
+        self._check(lib().gs_get_mesh_series(self.ctx, _ptr(se, u64), rows.value))
+        return se
+
+    def write_mesh_metrics(self, path):
+        """Every peer's go-node GRAFT / PRUNE counters and mesh gauges after a mesh_converge with
+        set_mesh_events."""
+        write_mesh_metrics(self.cfg, path, self.csr()[0], self.mesh()[1], self.mesh_events())
+
+    def write_mesh_series(self, path):
+        write_mesh_series(path, self.mesh_series())
 
     # ---- per-peer pubsub event counts (gs_set_pubsub_counts, DESIGN.md §2.14) ----
     def set_pubsub_counts(self, on=True):

@@ -26,12 +26,14 @@ void usage() {
           "         [--delay-ms MS] [--t0-s SECONDS] [--http-us US] [--max-heartbeats H] [--latencies PATH]\n"
           "         [--device-log]\n"
           "         [--gml network_topology.gml --yaml shadow.yaml] [--schedule FILE] [--shadowlog PATH] [--metrics PATH]\n"
-          "         [--testnode-metrics PATH] [--pubsub-metrics PATH]\n"
+          "         [--testnode-metrics PATH] [--pubsub-metrics PATH] [--mesh-metrics PATH] [--mesh-series PATH]\n"
           "  --yaml also supplies the injector's -s/-m/-d and start_time unless given on the command line\n"
           "  --device-log writes --latencies from the device-formatted text (gs_run_log), one fwrite per chunk\n"
           "  --testnode-metrics writes the nim node's per-peer delay metrics (dst_testnode_*, gs_set_peer_delay);\n"
           "    a run with a latency of 65535 ms or more then fails\n"
           "  --pubsub-metrics writes the go node's per-peer pubsub counters (libp2p_pubsub_*, gs_set_pubsub_counts)\n"
+          "  --mesh-metrics writes the go node's per-peer GRAFT / PRUNE counters and mesh gauges, --mesh-series the\n"
+          "    per-epoch mesh health as CSV, both of the mesh convergence (gs_set_mesh_events)\n"
           "env: PEERS CONNECTTO FRAGMENTS MUXER MAXCONNECTIONS GOSSIPSUB_* SELFTRIGGER GS_NODE GS_SEED GS_BATCH\n"
           "     GS_DEVICE\n");
 }
@@ -118,7 +120,7 @@ int main(int argc, char** argv) {
   // the POST reaches the node 1.5 round trips over the 1 ms injector-hub links
   // after the injector sends it (topogen.py:64-69); tx_time is stamped then
   uint64_t http_us = 3000;
-  std::string latencies, gml, yaml, shadowlog, metrics, schedule, testnode, pubsub;
+  std::string latencies, gml, yaml, shadowlog, metrics, schedule, testnode, pubsub, mesh_metrics, mesh_series;
   bool set_size = false, set_msgs = false, set_delay = false, set_t0 = false, device_log = false;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -148,6 +150,8 @@ int main(int argc, char** argv) {
     else if (a == "--metrics") metrics = next();    // the node metrics (rust-test-node/src/metrics.rs)
     else if (a == "--testnode-metrics") testnode = next();  // the nim node's metrics (gossipsub-queues/main.nim:25-78)
     else if (a == "--pubsub-metrics") pubsub = next();  // the go node's pubsub counters (go-test-node/metrics.go:84-220)
+    else if (a == "--mesh-metrics") mesh_metrics = next();  // the go node's GRAFT / PRUNE counters (metrics.go:164-190)
+    else if (a == "--mesh-series") mesh_series = next();    // per-epoch mesh health (its tracer, metrics.go:224-258)
     else if (a == "--schedule") schedule = next();  // rows: t_pub_ns publisher msg_size [frags]
     else { usage(); return 2; }
   }
@@ -191,9 +195,28 @@ int main(int argc, char** argv) {
   if (counters && (st = gs_set_traffic(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_traffic");
   if (!testnode.empty() && (st = gs_set_peer_delay(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_peer_delay");
   if (!pubsub.empty() && (st = gs_set_pubsub_counts(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_pubsub_counts");
+  const bool mesh_events = !mesh_metrics.empty() || !mesh_series.empty();
+  if (mesh_events && (st = gs_set_mesh_events(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_mesh_events");
   if ((st = gs_build_topology(ctx)) != GS_OK) return die(ctx, st, "gs_build_topology");
   uint32_t epochs = 0;
   if ((st = gs_mesh_converge(ctx, max_hb, &epochs)) != GS_OK) return die(ctx, st, "gs_mesh_converge");
+  if (!mesh_metrics.empty()) {  // the events of the convergence, the mesh it ended with
+    std::vector<uint64_t> row((size_t)cfg.peers + 1), ev((size_t)cfg.peers * GS_MESH_EVENT_COLS);
+    std::vector<uint8_t> mc(cfg.peers);
+    if ((st = gs_get_csr(ctx, row.data(), nullptr, nullptr)) != GS_OK) return die(ctx, st, "gs_get_csr");
+    if ((st = gs_get_mesh(ctx, nullptr, mc.data())) != GS_OK) return die(ctx, st, "gs_get_mesh");
+    if ((st = gs_get_mesh_events(ctx, ev.data())) != GS_OK) return die(ctx, st, "gs_get_mesh_events");
+    st = gs_write_mesh_metrics(&cfg, mesh_metrics.c_str(), cfg.peers, row.data(), mc.data(), ev.data());
+    if (st != GS_OK) return die(ctx, st, "gs_write_mesh_metrics");
+  }
+  if (!mesh_series.empty()) {
+    uint32_t rows = 0;
+    if ((st = gs_mesh_series_rows(ctx, &rows)) != GS_OK) return die(ctx, st, "gs_mesh_series_rows");
+    std::vector<uint64_t> se((size_t)rows * GS_MESH_SERIES_COLS);
+    if ((st = gs_get_mesh_series(ctx, se.data(), rows)) != GS_OK) return die(ctx, st, "gs_get_mesh_series");
+    if ((st = gs_write_mesh_series(mesh_series.c_str(), se.data(), rows)) != GS_OK)
+      return die(ctx, st, "gs_write_mesh_series");
+  }
 
   std::vector<gs_publish> sched;
   if (!schedule.empty()) {  // an explicit publish schedule stands in for the HTTP injector

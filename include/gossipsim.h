@@ -518,6 +518,81 @@ gs_status gs_reset_pubsub_counts(struct gs_ctx* ctx);
  * (gs_get_pubsub_counts). Host only. */
 gs_status gs_write_pubsub_metrics(const gs_config* cfg, const char* path, uint32_t peers, const uint64_t* counts);
 
+/* ---- mesh events and per-epoch mesh health -----------------
+ * What go-test-node/metrics.go:164-190 counts per node (GRAFT and PRUNE RPCs
+ * sent and received) and what its tracer follows (metrics.go:224-258 mesh size,
+ * Graft / Prune; 328-362 topic health), for the epochs one gs_mesh_converge call
+ * steps. The rules are those of DESIGN.md §2.3 (steps A, B, C) and the
+ * disconnect of §2.8. An entry e = (u -> w) is a CSR entry of row u. */
+enum { GS_ME_GRAFT_TX = 0,  /* entries of u that carry a GRAFT after step A (subscription grafts, */
+                            /* the D - m grafts, the outbound grafts)                            */
+       GS_ME_GRAFT_RX = 1,  /* neighbours' GRAFTs that target u (the ones step B handles)        */
+       GS_ME_PRUNE_TX = 2,  /* u's step-A PRUNEs + the GRAFTs u rejects in B (the PRUNE reply:   */
+                            /* back-off not over, or at D_hi and the grafter not dialed by u)    */
+       GS_ME_PRUNE_RX = 3,  /* neighbours' step-A PRUNEs of u + u's own GRAFTs that were rejected */
+       GS_ME_MESH_ADD = 4,  /* entries of u outside the mesh after the epoch's disconnect and in */
+                            /* it after C (both ends of a new link count their own entry)        */
+       GS_ME_MESH_DEL = 5,  /* entries of u in the mesh after the disconnect and out of it after */
+                            /* C: a PRUNE sent or received (entries, not RPCs)                   */
+       GS_ME_MESH_DROP = 6, /* entries of u in the mesh at the start of the epoch whose either   */
+                            /* end is offline in it (§2.8: no PRUNE, no back-off; an offline     */
+                            /* peer counts its own entries too)                                  */
+       GS_MESH_EVENT_COLS = 7 };
+/* One series row per epoch h = 0..out_epochs, the state after step C. */
+enum { GS_MS_ONLINE = 0,    /* peers online in epoch h                                           */
+       GS_MS_NO_PEERS = 1,  /* online peers with mesh size 0                                     */
+       GS_MS_LOW = 2,       /* online peers with 0 < m < D_lo                                    */
+       GS_MS_HEALTHY = 3,   /* online peers with m >= D_lo (the three classes: metrics.go:348-362) */
+       GS_MS_OVER = 4,      /* online peers with m > D_hi (a subset of HEALTHY)                  */
+       GS_MS_LINKS = 5,     /* sum of m over all peers                                           */
+       GS_MS_GRAFTS = 6,    /* GRAFT proposals in the epoch                                      */
+       GS_MS_REJECTS = 7,   /* GRAFTs rejected in B                                              */
+       GS_MS_PRUNES = 8,    /* step-A PRUNEs                                                     */
+       GS_MS_DROPS = 9,     /* entries dropped by the disconnect                                 */
+       GS_MS_ADDS = 10,     /* entries that entered the mesh                                     */
+       GS_MS_DELS = 11,     /* entries that left it by PRUNE                                     */
+       GS_MESH_SERIES_COLS = 12 };
+/* 1: gs_mesh_converge records both results for the epochs it steps from the
+ * empty mesh: epoch 0 (the subscription exchange; empty when sub_graft is 0)
+ * and heartbeats 1..out_epochs (frozen mesh: up to the fixed point, with its
+ * exact jumps over quiescent epochs; churn: exactly max_heartbeats). One more
+ * row kernel per stepped epoch; off by default, diagnostic. Every converge call
+ * zeroes and refills both, so they describe the last call, for all peers
+ * whatever partition the context holds (the mesh is replicated). The epochs
+ * gs_run's churn chain steps or replays later are NOT counted (it replays from
+ * epoch 0 and may drop a run it stepped ahead): converge to the horizon you
+ * want to read. Enabling allocates. gs_save_state does not carry the results:
+ * a loaded context has the switch off. */
+gs_status gs_set_mesh_events(struct gs_ctx* ctx, uint32_t enable);
+/* out[peers][GS_MESH_EVENT_COLS]. GS_ESTATE while the switch is off or before a
+ * converge ran since it went on (the two calls below as well). */
+gs_status gs_get_mesh_events(struct gs_ctx* ctx, uint64_t* out);
+/* *rows = out_epochs + 1 of the last converge. */
+gs_status gs_mesh_series_rows(struct gs_ctx* ctx, uint32_t* rows);
+/* out[rows][GS_MESH_SERIES_COLS]; GS_EINVAL unless rows is gs_mesh_series_rows'.
+ * An epoch the frozen-mesh jump skipped has no events and the previous row's
+ * gauges; with sub_graft = 0 row 0 is the empty mesh (ONLINE = NO_PEERS = peers). */
+gs_status gs_get_mesh_series(struct gs_ctx* ctx, uint64_t* out, uint32_t rows);
+
+/* The go node's GRAFT / PRUNE / subscription counters and mesh gauges
+ * (go-test-node/metrics.go:164-190 and 224-258, 328-362; help strings verbatim)
+ * for every peer in the Prometheus text exposition format, as
+ * gs_write_pubsub_metrics: libp2p_pubsub_broadcast_graft_total (GS_ME_GRAFT_TX),
+ * libp2p_pubsub_received_graft_total, libp2p_pubsub_broadcast_prune_total,
+ * libp2p_pubsub_received_prune_total, libp2p_pubsub_broadcast_subscriptions_total
+ * and libp2p_pubsub_received_subscriptions_total (both the CSR degree),
+ * libp2p_gossipsub_peers_per_topic_mesh (gauge, mesh_count),
+ * libp2p_gossipsub_low_peers_topics, libp2p_gossipsub_healthy_peers_topics and
+ * libp2p_gossipsub_no_peers_topics (gauges, 0 or 1 per peer against cfg->d_lo).
+ * row_ptr[peers + 1] (gs_get_csr), mesh_count[peers] (gs_get_mesh) and
+ * events[peers][GS_MESH_EVENT_COLS] (gs_get_mesh_events) are host copies. Host only. */
+gs_status gs_write_mesh_metrics(const gs_config* cfg, const char* path, uint32_t peers, const uint64_t* row_ptr,
+                                const uint8_t* mesh_count, const uint64_t* events);
+/* series[rows][GS_MESH_SERIES_COLS] (gs_get_mesh_series) as CSV: the header line
+ * epoch,online,no_peers,low,healthy,over,links,grafts,rejects,prunes,drops,adds,dels
+ * and one line per row. Host only. */
+gs_status gs_write_mesh_series(const char* path, const uint64_t* series, uint32_t rows);
+
 /* ---- what each node shows about delay ---------------------
  * The per-peer application metrics of nim-test-node/gossipsub-queues
  * (main.nim:25-78,147-154), reduced on the device from the logged latencies

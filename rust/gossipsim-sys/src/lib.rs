@@ -17,6 +17,8 @@ pub const GS_ABI_VERSION: u32 = 10;
 pub const GS_NODE_RUST: u32 = 0;
 pub const GS_TRAFFIC_COLS: usize = 12; // GS_TR_*: tx/rx bytes, packets, header bytes, received,
                                        // published, tx/rx ACK packets, tx/rx ACK header bytes
+pub const GS_MESH_EVENT_COLS: usize = 7; // GS_ME_*: graft tx/rx, prune tx/rx, mesh add/del/drop
+pub const GS_MESH_SERIES_COLS: usize = 12; // GS_MS_*: online, no_peers, low, healthy, over, links, then the six event sums
 pub const GS_PUBSUB_COLS: usize = 8; // GS_PS_*: msg tx/rx, first, dup, ihave tx/rx, iwant tx/rx
 pub const GS_HIST_BINS: usize = 64;
 pub const GS_DELAY_BUCKETS: usize = 12; // le = 1 .. 10000 ms (nim gossipsub-queues main.nim:59)
@@ -149,6 +151,13 @@ extern "C" {
     pub fn gs_reset_pubsub_counts(ctx: *mut gs_ctx) -> gs_status;
     pub fn gs_write_pubsub_metrics(cfg: *const gs_config, path: *const c_char, peers: u32, counts: *const u64)
                                    -> gs_status;
+    pub fn gs_set_mesh_events(ctx: *mut gs_ctx, enable: u32) -> gs_status;
+    pub fn gs_get_mesh_events(ctx: *mut gs_ctx, out: *mut u64) -> gs_status;
+    pub fn gs_mesh_series_rows(ctx: *mut gs_ctx, rows: *mut u32) -> gs_status;
+    pub fn gs_get_mesh_series(ctx: *mut gs_ctx, out: *mut u64, rows: u32) -> gs_status;
+    pub fn gs_write_mesh_metrics(cfg: *const gs_config, path: *const c_char, peers: u32, row_ptr: *const u64,
+                                 mesh_count: *const u8, events: *const u64) -> gs_status;
+    pub fn gs_write_mesh_series(path: *const c_char, series: *const u64, rows: u32) -> gs_status;
     pub fn gs_set_peer_delay(ctx: *mut gs_ctx, enable: u32) -> gs_status;
     pub fn gs_get_peer_delay(ctx: *mut gs_ctx, out: *mut gs_peer_delay) -> gs_status;
     pub fn gs_reset_peer_delay(ctx: *mut gs_ctx) -> gs_status;
