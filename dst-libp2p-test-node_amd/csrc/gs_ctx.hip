@@ -189,6 +189,28 @@ extern "C" gs_status gs_build_topology(gs_ctx* ctx) {
   ctx->cell_valid = false;
   ctx->mesh_built = false;
   ctx->glp_prefer = false;
+  if (ctx->topo_fp) graph_replaced(*ctx);  // the graph before was an imported one, another than this
+  ctx->topo_fp = 0;
+  GS_API_END(ctx)
+}
+
+// ---- a caller's graph in place of the built one (gs_topology.hip) ----
+extern "C" gs_status gs_set_topology(gs_ctx* ctx, const uint64_t* row_ptr, const uint32_t* col, const uint8_t* flags) {
+  GS_API_BEGIN(ctx)
+  if (!row_ptr) ctx->fail(GS_EINVAL, "null row_ptr");
+  if (ctx->part_open) ctx->fail(GS_ESTATE, "a partitioned batch is in flight (gs_part_finish first)");
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  import_csr(*ctx, row_ptr, col, flags);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_set_topology_dials(gs_ctx* ctx, uint64_t n_dials, const uint32_t* dialer,
+                                           const uint32_t* target) {
+  GS_API_BEGIN(ctx)
+  if (n_dials && (!dialer || !target)) ctx->fail(GS_EINVAL, "null dial arrays");
+  if (ctx->part_open) ctx->fail(GS_ESTATE, "a partitioned batch is in flight (gs_part_finish first)");
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  import_dials(*ctx, n_dials, dialer, target);
   GS_API_END(ctx)
 }
 

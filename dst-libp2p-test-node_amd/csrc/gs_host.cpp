@@ -609,6 +609,63 @@ extern "C" gs_status gs_read_schedule(const char* path, gs_publish* out, uint64_
   return rows > cap ? GS_ERANGE : GS_OK;
 }
 
+// A dial list file: "dialer target" per line (the accepted dials of connect_gossipsub_peers,
+// main.rs:340-348), comments and blank lines and the cap contract as gs_read_schedule.
+extern "C" gs_status gs_read_dials(const char* path, uint32_t* dialer, uint32_t* target, uint64_t cap, uint64_t* n) {
+  if (!path || !n) return GS_EINVAL;
+  FILE* f = fopen(path, "r");
+  if (!f) return GS_EINVAL;
+  char* line = nullptr;  // (whole lines of any length: getline)
+  size_t line_cap = 0;
+  uint64_t rows = 0;
+  gs_status st = GS_OK;
+  while (getline(&line, &line_cap, f) != -1) {
+    char* h = strchr(line, '#');
+    if (h) *h = 0;
+    char* q = line;
+    while (*q && isspace((unsigned char)*q)) q++;
+    if (!*q) continue;  // blank / comment
+    unsigned long long v[2] = {0, 0};
+    bool ok = true;
+    for (int k = 0; k < 2 && ok; k++) {
+      while (*q && isspace((unsigned char)*q)) q++;
+      ok = isdigit((unsigned char)*q) != 0;  // (strtoull alone would take a sign)
+      if (!ok) break;
+      char* end = nullptr;
+      v[k] = strtoull(q, &end, 10);
+      ok = end != q && v[k] <= 0xFFFFFFFFull && (!*end || isspace((unsigned char)*end));
+      q = end;
+    }
+    while (ok && *q && isspace((unsigned char)*q)) q++;
+    if (!ok || *q) { st = GS_EINVAL; break; }  // not a number, one column, or more than two
+    if (dialer && target && rows < cap) {
+      dialer[rows] = (uint32_t)v[0];
+      target[rows] = (uint32_t)v[1];
+    }
+    rows++;
+  }
+  free(line);
+  fclose(f);
+  *n = rows;
+  if (st != GS_OK) return st;
+  return rows > cap ? GS_ERANGE : GS_OK;
+}
+
+// One "dialer target" line per F_OUT entry of the CSR, in row order.
+extern "C" gs_status gs_write_dials(const char* path, uint32_t peers, const uint64_t* row_ptr, const uint32_t* col,
+                                    const uint8_t* flags) {
+  if (!path || !row_ptr || (row_ptr[peers] && (!col || !flags))) return GS_EINVAL;
+  FILE* f = fopen(path, "w");
+  if (!f) return GS_EINVAL;
+  std::vector<char> buf(1 << 20);
+  setvbuf(f, buf.data(), _IOFBF, buf.size());
+  for (uint32_t u = 0; u < peers; u++)
+    for (uint64_t e = row_ptr[u]; e < row_ptr[u + 1]; e++)
+      if (flags[e] & 1) fprintf(f, "%u %u\n", u, col[e]);
+  const bool bad = ferror(f) != 0;
+  return (fclose(f) != 0 || bad) ? GS_EINVAL : GS_OK;
+}
+
 // The node's custom metrics (rust-test-node/src/metrics.rs:60-132, names shared
 // with go metrics.go and nim gossipsub-queues/main.nim:25-78) for every peer,
 // in prometheus-client's OpenMetrics text encoding (the format store_metrics

@@ -180,6 +180,7 @@ struct Ctx {
   uint32_t k = 0;            // dials per peer
   uint64_t nnz = 0;
   uint32_t max_degree = 0;
+  uint64_t topo_fp = 0;      // fingerprint of an imported graph (gs_set_topology*); 0: gs_build_topology's
   DevBuf<uint8_t> d_stage;
   DevBuf<uint32_t> d_dial;   // [N*k]
   DevBuf<uint8_t> d_acc;     // [N*k] dial accepted
@@ -455,6 +456,9 @@ void check_sink(Ctx& c, const gs_result_sink* sink);  // gs_ctx.hip: gs_run's ru
 
 // ---- launchers (gs_topology.hip / gs_mesh.hip / gs_relax.hip) ----
 void launch_topology(Ctx& c);
+void import_csr(Ctx& c, const uint64_t* row_ptr, const uint32_t* col, const uint8_t* flags);  // gs_set_topology
+void import_dials(Ctx& c, uint64_t n, const uint32_t* dialer, const uint32_t* target);        // gs_set_topology_dials
+void graph_replaced(Ctx& c);  // the context holds another graph than before (an import, a build after one)
 uint32_t run_mesh(Ctx& c, uint32_t max_heartbeats);
 inline void ensure_cus(Ctx& c) {
   if (c.num_cus == 0) {

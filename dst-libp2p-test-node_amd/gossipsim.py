@@ -159,6 +159,10 @@ SIGNATURES = {
     "gs_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
     "gs_set_links": (i32, [ctypes.c_void_p, u32, P(u64), P(u64), P(u64), P(u8)]),
     "gs_build_topology": (i32, [ctypes.c_void_p]),
+    "gs_set_topology": (i32, [ctypes.c_void_p, P(u64), P(u32), P(u8)]),
+    "gs_set_topology_dials": (i32, [ctypes.c_void_p, u64, P(u32), P(u32)]),
+    "gs_read_dials": (i32, [ctypes.c_char_p, P(u32), P(u32), u64, P(u64)]),
+    "gs_write_dials": (i32, [ctypes.c_char_p, u32, P(u64), P(u32), P(u8)]),
     "gs_graph_info": (i32, [ctypes.c_void_p, P(u32), P(u64), P(u32)]),
     "gs_get_csr": (i32, [ctypes.c_void_p, P(u64), P(u32), P(u8)]),
     "gs_mesh_converge": (i32, [ctypes.c_void_p, u32, P(u32)]),
@@ -415,6 +419,72 @@ def read_schedule(path):
     return out
 
 
+def _fits(a, nbytes):
+    """An integer (or bool) array's values fit `nbytes` unsigned bytes (no pass over unsigned arrays that narrow)."""
+    if a.size == 0 or a.dtype.kind == "b" or (a.dtype.kind == "u" and a.dtype.itemsize <= nbytes):
+        return True
+    return int(a.min()) >= 0 and int(a.max()) < (1 << (8 * nbytes))
+
+
+def _csr_arrays(row_ptr, col, flags, peers=None):
+    """A CSR's three arrays as gs_set_topology / gs_write_dials take them; dtype and shape errors raise here."""
+    row, col, flags = np.asarray(row_ptr), np.asarray(col), np.asarray(flags)
+    for name, a, kinds in (("row_ptr", row, "ui"), ("col", col, "ui"), ("flags", flags, "uib")):
+        if a.ndim != 1:
+            raise ValueError("%s must be one-dimensional" % name)
+        if a.dtype.kind not in kinds and a.size:
+            raise TypeError("%s must hold integers, not %s" % (name, a.dtype))
+    if row.size < 2 or (peers is not None and row.size != peers + 1):
+        raise ValueError("row_ptr must have peers + 1 entries")
+    if row.size and row.dtype.kind == "i" and (row < 0).any():
+        raise ValueError("row_ptr must not be negative")
+    if not _fits(col, 4):
+        raise ValueError("col must fit 32 unsigned bits")
+    if not _fits(flags, 1):
+        raise ValueError("flags must fit 8 unsigned bits")
+    row = np.ascontiguousarray(row, np.uint64)
+    if col.shape != flags.shape or col.size != int(row[-1]):
+        raise ValueError("col and flags must have row_ptr[-1] entries each")
+    pad = 1 if col.size == 0 else 0  # (a pointer to take)
+    return (row, np.ascontiguousarray(np.resize(col, col.size + pad), np.uint32),
+            np.ascontiguousarray(np.resize(flags, flags.size + pad), np.uint8))
+
+
+def _dial_arrays(dialer, target):
+    d, t = np.asarray(dialer), np.asarray(target)
+    for name, a in (("dialer", d), ("target", t)):
+        if a.ndim != 1:
+            raise ValueError("%s must be one-dimensional" % name)
+        if a.size and a.dtype.kind not in "ui":
+            raise TypeError("%s must hold integers, not %s" % (name, a.dtype))
+        if not _fits(a, 4):
+            raise ValueError("%s must fit 32 unsigned bits" % name)
+    if d.shape != t.shape:
+        raise ValueError("dialer and target must have the same length")
+    return np.ascontiguousarray(d, np.uint32), np.ascontiguousarray(t, np.uint32)
+
+
+def read_dials(path):
+    """Dial list file, one "dialer target" pair per line -> (dialer, target) uint32 arrays (gs_read_dials)."""
+    n = u64()
+    rc = lib().gs_read_dials(str(path).encode(), None, None, 0, ctypes.byref(n))
+    if rc not in (0, GS_ERANGE):
+        raise GossipSimError(rc, "malformed dial list %s" % path)
+    d, t = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
+    rc = lib().gs_read_dials(str(path).encode(), _ptr(d, u32), _ptr(t, u32), n.value, ctypes.byref(n))
+    if rc:
+        raise GossipSimError(rc, "malformed dial list %s" % path)
+    return d[:n.value], t[:n.value]
+
+
+def write_dials(path, row_ptr, col, flags):
+    """One "dialer target" line per entry whose flags bit 0 is set, in row order (gs_write_dials)."""
+    row, col, flags = _csr_arrays(row_ptr, col, flags)
+    rc = lib().gs_write_dials(str(path).encode(), len(row) - 1, _ptr(row, u64), _ptr(col, u32), _ptr(flags, u8))
+    if rc:
+        raise GossipSimError(rc, "cannot write the dial list %s" % path)
+
+
 # Schedule constants of the benchmark workload: Shadow epoch 2000-01-01 plus the
 # injector start (shadow/topogen.py:130), 1000 ms spacing and publisher
 # (6 + i) mod N with rotation (shadow/README.md:57, run.sh:34-36). The injector
@@ -559,6 +629,19 @@ class Simulator:
         self._check(lib().gs_build_topology(self.ctx))
 
     build_topology = connect_gossipsub_peers
+
+    def set_topology(self, row_ptr, col, flags):
+        """A caller's graph in csr()'s layout in place of the built one (gs_set_topology); of flags
+        only bit 0 is read. A refused graph leaves the simulator as it was."""
+        row, col, flags = _csr_arrays(row_ptr, col, flags, self.peers)
+        self._check(lib().gs_set_topology(self.ctx, _ptr(row, u64), _ptr(col, u32), _ptr(flags, u8)))
+
+    def set_dials(self, dialer, target):
+        """The undirected union of the dials dialer[i] -> target[i], in any order (gs_set_topology_dials)."""
+        d, t = _dial_arrays(dialer, target)
+        pad = 1 if d.size == 0 else 0
+        self._check(lib().gs_set_topology_dials(self.ctx, d.size, _ptr(np.resize(d, d.size + pad), u32),
+                                                _ptr(np.resize(t, t.size + pad), u32)))
 
     def graph_info(self):
         n, nnz, md = u32(), u64(), u32()

@@ -27,6 +27,9 @@ void usage() {
           "         [--device-log]\n"
           "         [--gml network_topology.gml --yaml shadow.yaml] [--schedule FILE] [--shadowlog PATH] [--metrics PATH]\n"
           "         [--testnode-metrics PATH] [--pubsub-metrics PATH] [--mesh-metrics PATH] [--mesh-series PATH]\n"
+          "         [--topology DIALS] [--dump-topology PATH]\n"
+          "  --topology imports a dial list (one \"dialer target\" per line) in place of the random dialing;\n"
+          "    --dump-topology writes the dial list of the graph the run used\n"
           "  --yaml also supplies the injector's -s/-m/-d and start_time unless given on the command line\n"
           "  --device-log writes --latencies from the device-formatted text (gs_run_log), one fwrite per chunk\n"
           "  --testnode-metrics writes the nim node's per-peer delay metrics (dst_testnode_*, gs_set_peer_delay);\n"
@@ -121,6 +124,7 @@ int main(int argc, char** argv) {
   // after the injector sends it (topogen.py:64-69); tx_time is stamped then
   uint64_t http_us = 3000;
   std::string latencies, gml, yaml, shadowlog, metrics, schedule, testnode, pubsub, mesh_metrics, mesh_series;
+  std::string topology, dump_topology;
   bool set_size = false, set_msgs = false, set_delay = false, set_t0 = false, device_log = false;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -152,6 +156,8 @@ int main(int argc, char** argv) {
     else if (a == "--pubsub-metrics") pubsub = next();  // the go node's pubsub counters (go-test-node/metrics.go:84-220)
     else if (a == "--mesh-metrics") mesh_metrics = next();  // the go node's GRAFT / PRUNE counters (metrics.go:164-190)
     else if (a == "--mesh-series") mesh_series = next();    // per-epoch mesh health (its tracer, metrics.go:224-258)
+    else if (a == "--topology") topology = next();  // a dial list ("dialer target" per line) in place of the built graph
+    else if (a == "--dump-topology") dump_topology = next();  // the dial list of the graph the run used
     else if (a == "--schedule") schedule = next();  // rows: t_pub_ns publisher msg_size [frags]
     else { usage(); return 2; }
   }
@@ -197,7 +203,26 @@ int main(int argc, char** argv) {
   if (!pubsub.empty() && (st = gs_set_pubsub_counts(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_pubsub_counts");
   const bool mesh_events = !mesh_metrics.empty() || !mesh_series.empty();
   if (mesh_events && (st = gs_set_mesh_events(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_mesh_events");
-  if ((st = gs_build_topology(ctx)) != GS_OK) return die(ctx, st, "gs_build_topology");
+  if (topology.empty()) {
+    if ((st = gs_build_topology(ctx)) != GS_OK) return die(ctx, st, "gs_build_topology");
+  } else {  // the connections a real run made (its dial log lines, main.rs:340-348)
+    uint64_t rows = 0;
+    st = gs_read_dials(topology.c_str(), nullptr, nullptr, 0, &rows);
+    if (st != GS_OK && st != GS_ERANGE) { fprintf(stderr, "malformed dial list %s\n", topology.c_str()); return die(ctx, st, "gs_read_dials"); }
+    std::vector<uint32_t> dialer(rows + 1), target(rows + 1);
+    if ((st = gs_read_dials(topology.c_str(), dialer.data(), target.data(), rows, &rows)) != GS_OK) return die(ctx, st, "gs_read_dials");
+    if ((st = gs_set_topology_dials(ctx, rows, dialer.data(), target.data())) != GS_OK) return die(ctx, st, "gs_set_topology_dials");
+  }
+  if (!dump_topology.empty()) {
+    uint64_t nnz = 0;
+    if ((st = gs_graph_info(ctx, nullptr, &nnz, nullptr)) != GS_OK) return die(ctx, st, "gs_graph_info");
+    std::vector<uint64_t> row((size_t)cfg.peers + 1);
+    std::vector<uint32_t> col(nnz + 1);
+    std::vector<uint8_t> fl(nnz + 1);
+    if ((st = gs_get_csr(ctx, row.data(), col.data(), fl.data())) != GS_OK) return die(ctx, st, "gs_get_csr");
+    if ((st = gs_write_dials(dump_topology.c_str(), cfg.peers, row.data(), col.data(), fl.data())) != GS_OK)
+      return die(ctx, st, "gs_write_dials");
+  }
   uint32_t epochs = 0;
   if ((st = gs_mesh_converge(ctx, max_hb, &epochs)) != GS_OK) return die(ctx, st, "gs_mesh_converge");
   if (!mesh_metrics.empty()) {  // the events of the convergence, the mesh it ended with

@@ -23,7 +23,10 @@ Percentiles use the simulator's nearest-rank rule (gs_msg_summary: the value at
 rank ceil(q * n) of the sorted latencies), so a perfect simulator scores 0.
 
     python shadow_parity.py --latencies latencies1 --yaml shadow.yaml \\
-        --gml network_topology.gml --peers 100 --msg-size 15000 [--json out.json]
+        --gml network_topology.gml --peers 100 --msg-size 15000 [--json out.json] [--dials dials.txt]
+
+The reference dials with an unseeded RNG (main.rs:308), so no seed reproduces a run's
+graph: --dials replays the connections the run made (gossipsim.read_dials' format).
 
 The simulation itself runs on the GPU through the C ABI (gossipsim.Simulator,
 run(summary=True): the percentiles come from the device's gs_msg_summary).
@@ -146,6 +149,16 @@ def compare(shadow, sim, tol=0.05):
             "per_message": rows}
 
 
+def connect(sim, dials=None):
+    """The peer graph: the dial list file `dials` (the connections the Shadow run itself made, one
+    "dialer target" per line, the nodes' dial log lines main.rs:340-348) or, without one,
+    connect_gossipsub_peers()."""
+    if dials is None:
+        return sim.connect_gossipsub_peers()
+    import gossipsim
+    sim.set_dials(*gossipsim.read_dials(dials))
+
+
 def run(args):
     import gossipsim
     per = read_latencies(args.latencies)
@@ -164,12 +177,12 @@ def run(args):
     else:
         S, bl, bh, ll, lh = [int(x) for x in args.topogen.split(",")]
         sim.set_topogen_links(S, bl, bh, ll, lh, shortest=args.shortest)
-    sim.connect_gossipsub_peers()
+    connect(sim, args.dials)
     sim.mesh_converge()
     res = sim.run(sched, collect=False, summary=True)
     rep = compare(summarize(per), sim_summary(res["summary"], sched), args.tol)
     rep["config"] = {"peers": args.peers, "msg_size": msg_size, "fragments": args.fragments, "seed": args.seed,
-                     "links": args.gml or args.topogen, "latencies": args.latencies}
+                     "links": args.gml or args.topogen, "latencies": args.latencies, "dials": args.dials}
     return rep
 
 
@@ -184,6 +197,8 @@ def main(argv=None):
     ap.add_argument("--msg-size", type=int, default=0)
     ap.add_argument("--fragments", type=int, default=1)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dials", help="dial list file (\"dialer target\" per line): replay that graph instead of "
+                                    "connect_gossipsub_peers()")
     ap.add_argument("--node", choices=("rust", "go", "nim"), default="rust")
     ap.add_argument("--publisher-id", type=int, help="run.sh publisher_id (when the log cannot name one)")
     ap.add_argument("--rotation", type=int, default=0, help="run.sh publisher_rotation")

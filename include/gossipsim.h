@@ -401,7 +401,33 @@ gs_status gs_set_links(struct gs_ctx* ctx, uint32_t stages, const uint64_t* lat_
  * (replaces connect_gossipsub_peers, main.rs:303-389). */
 gs_status gs_build_topology(struct gs_ctx* ctx);
 
-/* Graph size after gs_build_topology. */
+/* A caller's graph in place of the built one: either call stands
+ * where gs_build_topology stands and may be repeated at any time; a converge must
+ * follow before the next run. connect_to, dial_extra and max_connections play no
+ * part. A refused graph (GS_EINVAL for a defect, GS_EUNSUPPORTED for a peer with
+ * more than 256 connections or >= 2^32 entries) leaves the context as it was;
+ * gs_last_error names the kind of defect and the smallest entry, dial or peer index
+ * that has it.
+ * gs_set_topology: the graph in gs_get_csr's layout, rows ascending by id; of flags
+ * only bit 0 ("the row's peer dialed col") is read. Every entry needs its reverse,
+ * every connection bit 0 on at least one end, every peer a connection. */
+gs_status gs_set_topology(struct gs_ctx* ctx, const uint64_t* row_ptr /*[peers+1]*/,
+                          const uint32_t* col, const uint8_t* flags);
+/* gs_set_topology_dials: the undirected union of the accepted dials dialer[i] ->
+ * target[i] (the "dialing" log lines, main.rs:340-348), in any order: the graph is a
+ * function of the set. u -> w and w -> u together are a mutual dial; the same
+ * ordered pair twice, dialer == target and a peer in no dial are defects. */
+gs_status gs_set_topology_dials(struct gs_ctx* ctx, uint64_t n_dials,
+                                const uint32_t* dialer, const uint32_t* target);
+/* Host only. A dial list as text: one "dialer target" pair per line, '#' comments
+ * and blank lines as gs_read_schedule, and its cap contract (GS_ERANGE with
+ * *n = rows when cap is too small; dialer and target may then be NULL). */
+gs_status gs_read_dials(const char* path, uint32_t* dialer, uint32_t* target, uint64_t cap, uint64_t* n);
+/* One line per entry with bit 0 set, in row order. */
+gs_status gs_write_dials(const char* path, uint32_t peers, const uint64_t* row_ptr,
+                         const uint32_t* col, const uint8_t* flags);
+
+/* Graph size after gs_build_topology or an import. */
 gs_status gs_graph_info(const struct gs_ctx* ctx, uint32_t* peers, uint64_t* nnz,
                         uint32_t* max_degree);
 

@@ -130,6 +130,13 @@ extern "C" {
     pub fn gs_set_links(ctx: *mut gs_ctx, stages: u32, lat_ns: *const u64, bw_up: *const u64,
                         bw_down: *const u64, stage_of_peer: *const u8) -> gs_status;
     pub fn gs_build_topology(ctx: *mut gs_ctx) -> gs_status;
+    pub fn gs_set_topology(ctx: *mut gs_ctx, row_ptr: *const u64, col: *const u32, flags: *const u8) -> gs_status;
+    pub fn gs_set_topology_dials(ctx: *mut gs_ctx, n_dials: u64, dialer: *const u32, target: *const u32)
+                                 -> gs_status;
+    pub fn gs_read_dials(path: *const c_char, dialer: *mut u32, target: *mut u32, cap: u64, n: *mut u64)
+                         -> gs_status;
+    pub fn gs_write_dials(path: *const c_char, peers: u32, row_ptr: *const u64, col: *const u32,
+                          flags: *const u8) -> gs_status;
     pub fn gs_graph_info(ctx: *const gs_ctx, peers: *mut u32, nnz: *mut u64, max_deg: *mut u32) -> gs_status;
     pub fn gs_get_csr(ctx: *mut gs_ctx, row_ptr: *mut u64, col: *mut u32, flags: *mut u8) -> gs_status;
     pub fn gs_mesh_converge(ctx: *mut gs_ctx, max_heartbeats: u32, epochs: *mut u32) -> gs_status;
