@@ -247,6 +247,34 @@ extern "C" gs_status gs_mesh_converge(gs_ctx* ctx, uint32_t max_heartbeats, uint
   GS_API_END(ctx)
 }
 
+// ---- a caller's mesh in place of the converged one (gs_meshimport.h) ----
+static void mesh_import_state(gs_ctx* ctx) {
+  if (!ctx->topo_built) ctx->fail(GS_ESTATE, "gs_build_topology first");
+  if (!ctx->links_set) ctx->fail(GS_ESTATE, "gs_set_links first");
+  if (ctx->part_open) ctx->fail(GS_ESTATE, "a partitioned batch is in flight (gs_part_finish first)");
+  if (ctx->cfg.churn_ppm)
+    ctx->fail(GS_EUNSUPPORTED, "an imported mesh under churn: every epoch's mesh comes from the chain, which starts "
+                               "from epoch 0 and has no place for an imported state (churn_ppm = 0, or gs_mesh_converge)");
+}
+
+extern "C" gs_status gs_set_mesh(gs_ctx* ctx, const uint32_t* mesh, const uint8_t* count) {
+  GS_API_BEGIN(ctx)
+  if (!mesh) ctx->fail(GS_EINVAL, "null mesh");
+  mesh_import_state(ctx);
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  import_mesh_ell(*ctx, mesh, count);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_set_mesh_links(gs_ctx* ctx, uint64_t n_links, const uint32_t* a, const uint32_t* b) {
+  GS_API_BEGIN(ctx)
+  if (n_links && (!a || !b)) ctx->fail(GS_EINVAL, "null link arrays");
+  mesh_import_state(ctx);
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  import_mesh_links(*ctx, n_links, a, b);
+  GS_API_END(ctx)
+}
+
 extern "C" gs_status gs_get_mesh(gs_ctx* ctx, uint32_t* mesh, uint8_t* count) {
   GS_API_BEGIN(ctx)
   if (!ctx->mesh_built) ctx->fail(GS_ESTATE, "gs_mesh_converge first");

@@ -666,6 +666,26 @@ extern "C" gs_status gs_write_dials(const char* path, uint32_t peers, const uint
   return (fclose(f) != 0 || bad) ? GS_EINVAL : GS_OK;
 }
 
+// One "a b" line per mesh link with a < b, in row order (gs_get_mesh's layout; a row is its first
+// count[u] slots, at most GS_MESH_W, or ends at its first UINT32_MAX): gs_read_dials reads it back.
+extern "C" gs_status gs_write_mesh_links(const char* path, uint32_t peers, const uint32_t* mesh, const uint8_t* count) {
+  if (!path || (peers && !mesh)) return GS_EINVAL;
+  FILE* f = fopen(path, "w");
+  if (!f) return GS_EINVAL;
+  std::vector<char> buf(1 << 20);
+  setvbuf(f, buf.data(), _IOFBF, buf.size());
+  for (uint32_t u = 0; u < peers; u++) {
+    const uint32_t n = count && count[u] < GS_MESH_W ? count[u] : GS_MESH_W;
+    for (uint32_t j = 0; j < n; j++) {
+      const uint32_t w = mesh[(size_t)u * GS_MESH_W + j];
+      if (!count && w == 0xFFFFFFFFu) break;
+      if (u < w && w != 0xFFFFFFFFu) fprintf(f, "%u %u\n", u, w);
+    }
+  }
+  const bool bad = ferror(f) != 0;
+  return (fclose(f) != 0 || bad) ? GS_EINVAL : GS_OK;
+}
+
 // The node's custom metrics (rust-test-node/src/metrics.rs:60-132, names shared
 // with go metrics.go and nim gossipsub-queues/main.nim:25-78) for every peer,
 // in prometheus-client's OpenMetrics text encoding (the format store_metrics

@@ -181,6 +181,7 @@ struct Ctx {
   uint64_t nnz = 0;
   uint32_t max_degree = 0;
   uint64_t topo_fp = 0;      // fingerprint of an imported graph (gs_set_topology*); 0: gs_build_topology's
+  uint64_t mesh_fp = 0;      // fingerprint of an imported mesh (gs_set_mesh*); 0: a converged or loaded one
   DevBuf<uint8_t> d_stage;
   DevBuf<uint32_t> d_dial;   // [N*k]
   DevBuf<uint8_t> d_acc;     // [N*k] dial accepted
@@ -460,6 +461,8 @@ void import_csr(Ctx& c, const uint64_t* row_ptr, const uint32_t* col, const uint
 void import_dials(Ctx& c, uint64_t n, const uint32_t* dialer, const uint32_t* target);        // gs_set_topology_dials
 void graph_replaced(Ctx& c);  // the context holds another graph than before (an import, a build after one)
 uint32_t run_mesh(Ctx& c, uint32_t max_heartbeats);
+void import_mesh_ell(Ctx& c, const uint32_t* mesh, const uint8_t* count);                  // gs_set_mesh
+void import_mesh_links(Ctx& c, uint64_t n, const uint32_t* a, const uint32_t* b);         // gs_set_mesh_links
 inline void ensure_cus(Ctx& c) {
   if (c.num_cus == 0) {
     hipDeviceProp_t prop;

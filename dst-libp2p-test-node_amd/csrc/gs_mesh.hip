@@ -18,6 +18,9 @@
 // a step only when the step can change it). gs_run keeps a ring of per-epoch
 // snapshots {mesh ELL, offline bitset, IHAVE targets} (slot = epoch mod R)
 // that the relaxation kernels index by the epoch each event falls in.
+#include <algorithm>
+
+#include "gs_import.h"
 #include "gs_internal.h"
 
 namespace gs {
@@ -1522,6 +1525,7 @@ uint32_t run_mesh(Ctx& c, uint32_t max_hb) {
   c.ring_in_tag.assign(c.ring_in_tag.size(), ~0ull);  // a new mesh: the churn ring restarts
   c.ring_ell_tag.assign(c.ring_ell_tag.size(), ~0ull);
   c.glp_prefer = false;  // and gossip batches try the eager pass + no-op proof first again
+  c.mesh_fp = 0;         // a converged mesh, whatever stood here before (gs_meshimport.h)
   // gs_set_mesh_events: the epochs this call steps are counted (not those gs_run's chain
   // steps or replays later); under churn the device holds every epoch's series row
   const bool count = c.meshev;
@@ -1593,5 +1597,7 @@ void mesh_events_get(Ctx& c, uint64_t* out) {
   for (size_t u = 0; u < N; u++)
     for (size_t k = 0; k < GS_MESH_EVENT_COLS; k++) out[u * GS_MESH_EVENT_COLS + k] = h[k * N + u];
 }
+
+#include "gs_meshimport.h"
 
 }  // namespace gs

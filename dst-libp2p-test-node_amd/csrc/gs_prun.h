@@ -202,6 +202,7 @@ struct PRun {
       for (uint64_t x : v) h = (h ^ x) * 1099511628211ull;
     }
     if (c.topo_fp) h = (h ^ c.topo_fp) * 1099511628211ull;  // an imported graph's fingerprint (0: the built one)
+    if (c.mesh_fp) h = (h ^ c.mesh_fp) * 1099511628211ull;  // an imported mesh's (0: a converged one)
     const uint64_t sig[8] = {c.cfg.peers, c.cfg.batch, c.cfg.lazy_gossip, c.cfg.idontwant,
                              c.cfg.churn_ppm, c.cfg.fragments, c.cfg.seed, h ^ n_msgs};
     static_assert(2 * sizeof sig <= HP_SCRATCH * 8, "the MIN and MAX rows in the mirror's scratch words");
@@ -217,7 +218,8 @@ struct PRun {
     for (int k = 0; k < 8; k++)
       if (c.h_pinned[k] != c.h_pinned[8 + k])
         throw Error(GS_EINVAL, "RCCL ranks disagree on the partitioned run (peers, batch, lazy_gossip, idontwant, "
-                               "churn, fragments, seed, schedule, the imported graph, the latency stream or gs_set_peer_delay)");
+                               "churn, fragments, seed, schedule, the imported graph, the latency stream or gs_set_peer_delay, "
+                               "the imported mesh)");
   }
 
   // ---- the u16 latencies of a batch ----
@@ -762,6 +764,8 @@ gs_status run_partitioned(gs_ctx* const* ctxs, uint32_t nctx, gs_comm* comm, con
       if (c.pdelay != c0->pdelay) c0->fail(GS_EINVAL, "every part needs the same gs_set_peer_delay switch");
       if (c.topo_fp != c0->topo_fp)  // (0: gs_build_topology's graph, a function of the configuration)
         c0->fail(GS_EINVAL, "every part needs the same graph (gs_set_topology / gs_set_topology_dials)");
+      if (c.mesh_fp != c0->mesh_fp)  // (0: a converged or loaded mesh; an import of the same mesh is not 0)
+        c0->fail(GS_EINVAL, "every part needs the same mesh (gs_set_mesh / gs_set_mesh_links in every part, or in none)");
       part_set(c, comm->nranks, r.me(i));
     });
     if (!comm->local && c0->cfg.device != comm->device)

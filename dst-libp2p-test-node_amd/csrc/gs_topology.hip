@@ -17,6 +17,7 @@
 
 #include <algorithm>
 
+#include "gs_import.h"
 #include "gs_internal.h"
 
 namespace gs {
@@ -182,10 +183,7 @@ __global__ __launch_bounds__(TB) void k_reverse(uint32_t N, const uint64_t* __re
 inline unsigned blocks(uint64_t n) { return (unsigned)((n + TB - 1) / TB); }
 
 // ---- import of a caller's graph (gs_set_topology, gs_set_topology_dials) ----
-// A defect is one word, kind << IMP_KIND_SHIFT | index, reduced with atomicMin: the smallest
-// kind and, of that kind, the smallest index, whatever order the threads run in.
-constexpr int IMP_KIND_SHIFT = 48;
-constexpr uint64_t IMP_NONE = ~0ull;
+// (the defect word and the fingerprint's mix: gs_import.h)
 enum : uint64_t {  // CSR defects, in reporting order (index: entry; CK_ALONE: peer)
   CK_RANGE = 1, CK_SELF = 2, CK_ORDER = 3, CK_NOREV = 4, CK_NODIALER = 5, CK_ALONE = 6
 };
@@ -194,17 +192,6 @@ enum : uint64_t {  // dial-list defects, in reporting order (index: dial; DK_ALO
 };
 constexpr uint32_t IMP_ENDS = 2 * MAX_DEG;  // dial ends of a valid row (every connection a mutual dial)
 constexpr uint32_t IMP_THREAD_ENDS = 64;    // rows up to here sort one thread per row
-
-__device__ inline void imp_defect(unsigned long long* err, uint64_t kind, uint64_t idx) {
-  atomicMin(err, (unsigned long long)((kind << IMP_KIND_SHIFT) | idx));
-}
-
-__device__ inline uint64_t imp_mix(uint64_t x) {  // splitmix64's finaliser
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 
 // Thread t checks entry t (t < nnz) and peer t (t < N): the defects of DESIGN.md §2.1, rev as
 // k_reverse finds it, the flags cut to F_OUT, the widest row. A row that is not ascending

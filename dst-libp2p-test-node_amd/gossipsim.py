@@ -167,6 +167,9 @@ SIGNATURES = {
     "gs_get_csr": (i32, [ctypes.c_void_p, P(u64), P(u32), P(u8)]),
     "gs_mesh_converge": (i32, [ctypes.c_void_p, u32, P(u32)]),
     "gs_get_mesh": (i32, [ctypes.c_void_p, P(u32), P(u8)]),
+    "gs_set_mesh": (i32, [ctypes.c_void_p, P(u32), P(u8)]),
+    "gs_set_mesh_links": (i32, [ctypes.c_void_p, u64, P(u32), P(u32)]),
+    "gs_write_mesh_links": (i32, [ctypes.c_char_p, u32, P(u32), P(u8)]),
     "gs_run": (i32, [ctypes.c_void_p, P(GsPublish), u64, P(GsResultSink)]),
     "gs_run_log": (i32, [ctypes.c_void_p, P(GsPublish), u64, TEXT_FN, ctypes.c_void_p, u64]),
     "gs_format_lat_log": (i32, [ctypes.c_void_p, P(GsPublish), u64, P(ctypes.c_uint16), TEXT_FN, ctypes.c_void_p,
@@ -450,9 +453,9 @@ def _csr_arrays(row_ptr, col, flags, peers=None):
             np.ascontiguousarray(np.resize(flags, flags.size + pad), np.uint8))
 
 
-def _dial_arrays(dialer, target):
+def _dial_arrays(dialer, target, names=("dialer", "target")):
     d, t = np.asarray(dialer), np.asarray(target)
-    for name, a in (("dialer", d), ("target", t)):
+    for name, a in zip(names, (d, t)):
         if a.ndim != 1:
             raise ValueError("%s must be one-dimensional" % name)
         if a.size and a.dtype.kind not in "ui":
@@ -460,8 +463,42 @@ def _dial_arrays(dialer, target):
         if not _fits(a, 4):
             raise ValueError("%s must fit 32 unsigned bits" % name)
     if d.shape != t.shape:
-        raise ValueError("dialer and target must have the same length")
+        raise ValueError("%s and %s must have the same length" % names)
     return np.ascontiguousarray(d, np.uint32), np.ascontiguousarray(t, np.uint32)
+
+
+def _mesh_arrays(mesh, count, peers=None):
+    """Mesh rows in Simulator.mesh()'s layout as gs_set_mesh / gs_write_mesh_links take them: [peers, MESH_W]
+    (or flat) ids, count[peers] or None; dtype and shape errors raise here."""
+    m = np.asarray(mesh)
+    if m.ndim not in (1, 2) or (m.ndim == 2 and m.shape[1] != MESH_W) or m.size % MESH_W:
+        raise ValueError("mesh must be [peers, %d] (or that many ids flat)" % MESH_W)
+    if m.size and m.dtype.kind not in "ui":
+        raise TypeError("mesh must hold integers, not %s" % m.dtype)
+    if not _fits(m, 4):
+        raise ValueError("mesh must fit 32 unsigned bits")
+    n = m.size // MESH_W
+    if n == 0 or (peers is not None and n != peers):
+        raise ValueError("mesh must have peers rows")
+    c = None
+    if count is not None:
+        c = np.asarray(count)
+        if c.ndim != 1 or c.size != n:
+            raise ValueError("count must have peers entries")
+        if c.dtype.kind not in "uib":
+            raise TypeError("count must hold integers, not %s" % c.dtype)
+        if not _fits(c, 1):
+            raise ValueError("count must fit 8 unsigned bits")
+        c = np.ascontiguousarray(c, np.uint8)
+    return np.ascontiguousarray(m.reshape(-1), np.uint32), c
+
+
+def write_mesh_links(path, mesh, count=None):
+    """One "a b" line per mesh link with a < b, in row order (gs_write_mesh_links); read_dials reads it back."""
+    m, c = _mesh_arrays(mesh, count)
+    rc = lib().gs_write_mesh_links(str(path).encode(), m.size // MESH_W, _ptr(m, u32), None if c is None else _ptr(c, u8))
+    if rc:
+        raise GossipSimError(rc, "cannot write the mesh links %s" % path)
 
 
 def read_dials(path):
@@ -667,6 +704,21 @@ class Simulator:
         c = np.zeros(self.peers, np.uint8)
         self._check(lib().gs_get_mesh(self.ctx, _ptr(m, u32), _ptr(c, u8)))
         return m.reshape(self.peers, MESH_W), c
+
+    def set_mesh(self, mesh, count=None):
+        """A caller's mesh in mesh()'s layout in place of the converged one (gs_set_mesh): ids in any order
+        inside a row; without count a row ends at its first 0xFFFFFFFF. A refused mesh leaves the simulator
+        as it was."""
+        m, c = _mesh_arrays(mesh, count, self.peers)
+        self._check(lib().gs_set_mesh(self.ctx, _ptr(m, u32), None if c is None else _ptr(c, u8)))
+
+    def set_mesh_links(self, a, b):
+        """The mesh as the set of undirected links {a[i], b[i]}, in any order and either orientation
+        (gs_set_mesh_links); no link is the empty mesh."""
+        a, b = _dial_arrays(a, b, ("a", "b"))
+        pad = 1 if a.size == 0 else 0
+        self._check(lib().gs_set_mesh_links(self.ctx, a.size, _ptr(np.resize(a, a.size + pad), u32),
+                                            _ptr(np.resize(b, b.size + pad), u32)))
 
     # ---- publish / run ----
     def publish(self, publisher, msg_size, t_pub_ns):

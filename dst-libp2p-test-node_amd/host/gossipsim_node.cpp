@@ -27,9 +27,12 @@ void usage() {
           "         [--device-log]\n"
           "         [--gml network_topology.gml --yaml shadow.yaml] [--schedule FILE] [--shadowlog PATH] [--metrics PATH]\n"
           "         [--testnode-metrics PATH] [--pubsub-metrics PATH] [--mesh-metrics PATH] [--mesh-series PATH]\n"
-          "         [--topology DIALS] [--dump-topology PATH]\n"
+          "         [--topology DIALS] [--dump-topology PATH] [--mesh LINKS] [--dump-mesh PATH]\n"
           "  --topology imports a dial list (one \"dialer target\" per line) in place of the random dialing;\n"
           "    --dump-topology writes the dial list of the graph the run used\n"
+          "  --mesh imports a mesh (one \"a b\" link per line) in place of the heartbeats' converge (not with\n"
+          "    --mesh-metrics / --mesh-series, which describe a converge); --dump-mesh writes the links of the mesh\n"
+          "    the run used\n"
           "  --yaml also supplies the injector's -s/-m/-d and start_time unless given on the command line\n"
           "  --device-log writes --latencies from the device-formatted text (gs_run_log), one fwrite per chunk\n"
           "  --testnode-metrics writes the nim node's per-peer delay metrics (dst_testnode_*, gs_set_peer_delay);\n"
@@ -124,7 +127,7 @@ int main(int argc, char** argv) {
   // after the injector sends it (topogen.py:64-69); tx_time is stamped then
   uint64_t http_us = 3000;
   std::string latencies, gml, yaml, shadowlog, metrics, schedule, testnode, pubsub, mesh_metrics, mesh_series;
-  std::string topology, dump_topology;
+  std::string topology, dump_topology, mesh_file, dump_mesh;
   bool set_size = false, set_msgs = false, set_delay = false, set_t0 = false, device_log = false;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -158,8 +161,15 @@ int main(int argc, char** argv) {
     else if (a == "--mesh-series") mesh_series = next();    // per-epoch mesh health (its tracer, metrics.go:224-258)
     else if (a == "--topology") topology = next();  // a dial list ("dialer target" per line) in place of the built graph
     else if (a == "--dump-topology") dump_topology = next();  // the dial list of the graph the run used
+    else if (a == "--mesh") mesh_file = next();  // a link list ("a b" per line) in place of the converge
+    else if (a == "--dump-mesh") dump_mesh = next();  // the links of the mesh the run used
     else if (a == "--schedule") schedule = next();  // rows: t_pub_ns publisher msg_size [frags]
     else { usage(); return 2; }
+  }
+  if (!mesh_file.empty() && (!mesh_metrics.empty() || !mesh_series.empty())) {  // (their getters: GS_ESTATE after an import)
+    fprintf(stderr, "--mesh cannot be combined with %s: the mesh events describe a converge\n",
+            mesh_metrics.empty() ? "--mesh-series" : "--mesh-metrics");
+    return 2;
   }
   gs_config cfg;
   gs_config_default(&cfg);
@@ -224,7 +234,23 @@ int main(int argc, char** argv) {
       return die(ctx, st, "gs_write_dials");
   }
   uint32_t epochs = 0;
-  if ((st = gs_mesh_converge(ctx, max_hb, &epochs)) != GS_OK) return die(ctx, st, "gs_mesh_converge");
+  if (mesh_file.empty()) {
+    if ((st = gs_mesh_converge(ctx, max_hb, &epochs)) != GS_OK) return die(ctx, st, "gs_mesh_converge");
+  } else {  // the mesh a real run ended up with (a tracer's Graft / Prune events, go metrics.go:328-340), or a what-if one
+    uint64_t rows = 0;
+    st = gs_read_dials(mesh_file.c_str(), nullptr, nullptr, 0, &rows);
+    if (st != GS_OK && st != GS_ERANGE) { fprintf(stderr, "malformed link list %s\n", mesh_file.c_str()); return die(ctx, st, "gs_read_dials"); }
+    std::vector<uint32_t> la(rows + 1), lb(rows + 1);
+    if ((st = gs_read_dials(mesh_file.c_str(), la.data(), lb.data(), rows, &rows)) != GS_OK) return die(ctx, st, "gs_read_dials");
+    if ((st = gs_set_mesh_links(ctx, rows, la.data(), lb.data())) != GS_OK) return die(ctx, st, "gs_set_mesh_links");
+  }
+  if (!dump_mesh.empty()) {
+    std::vector<uint32_t> m((size_t)cfg.peers * GS_MESH_W);
+    std::vector<uint8_t> mc(cfg.peers);
+    if ((st = gs_get_mesh(ctx, m.data(), mc.data())) != GS_OK) return die(ctx, st, "gs_get_mesh");
+    if ((st = gs_write_mesh_links(dump_mesh.c_str(), cfg.peers, m.data(), mc.data())) != GS_OK)
+      return die(ctx, st, "gs_write_mesh_links");
+  }
   if (!mesh_metrics.empty()) {  // the events of the convergence, the mesh it ended with
     std::vector<uint64_t> row((size_t)cfg.peers + 1), ev((size_t)cfg.peers * GS_MESH_EVENT_COLS);
     std::vector<uint8_t> mc(cfg.peers);

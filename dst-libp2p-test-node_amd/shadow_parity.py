@@ -23,10 +23,14 @@ Percentiles use the simulator's nearest-rank rule (gs_msg_summary: the value at
 rank ceil(q * n) of the sorted latencies), so a perfect simulator scores 0.
 
     python shadow_parity.py --latencies latencies1 --yaml shadow.yaml \\
-        --gml network_topology.gml --peers 100 --msg-size 15000 [--json out.json] [--dials dials.txt]
+        --gml network_topology.gml --peers 100 --msg-size 15000 [--json out.json] [--dials dials.txt] \\
+        [--mesh mesh.txt]
 
 The reference dials with an unseeded RNG (main.rs:308), so no seed reproduces a run's
 graph: --dials replays the connections the run made (gossipsim.read_dials' format).
+--mesh pins the mesh the run ended up with as well (one "a b" link per line, from a
+tracer's Graft / Prune events or the nodes' mesh peers): the comparison is then of the
+dissemination model alone, not of mesh formation plus dissemination.
 
 The simulation itself runs on the GPU through the C ABI (gossipsim.Simulator,
 run(summary=True): the percentiles come from the device's gs_msg_summary).
@@ -159,6 +163,15 @@ def connect(sim, dials=None):
     sim.set_dials(*gossipsim.read_dials(dials))
 
 
+def form_mesh(sim, mesh=None):
+    """The mesh: the link file `mesh` (the mesh the Shadow run ended up with, one "a b" per line) or,
+    without one, mesh_converge()."""
+    if mesh is None:
+        return sim.mesh_converge()
+    import gossipsim
+    sim.set_mesh_links(*gossipsim.read_dials(mesh))
+
+
 def run(args):
     import gossipsim
     per = read_latencies(args.latencies)
@@ -178,11 +191,12 @@ def run(args):
         S, bl, bh, ll, lh = [int(x) for x in args.topogen.split(",")]
         sim.set_topogen_links(S, bl, bh, ll, lh, shortest=args.shortest)
     connect(sim, args.dials)
-    sim.mesh_converge()
+    form_mesh(sim, args.mesh)
     res = sim.run(sched, collect=False, summary=True)
     rep = compare(summarize(per), sim_summary(res["summary"], sched), args.tol)
     rep["config"] = {"peers": args.peers, "msg_size": msg_size, "fragments": args.fragments, "seed": args.seed,
-                     "links": args.gml or args.topogen, "latencies": args.latencies, "dials": args.dials}
+                     "links": args.gml or args.topogen, "latencies": args.latencies, "dials": args.dials,
+                     "mesh": args.mesh}
     return rep
 
 
@@ -199,6 +213,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--dials", help="dial list file (\"dialer target\" per line): replay that graph instead of "
                                     "connect_gossipsub_peers()")
+    ap.add_argument("--mesh", help="mesh link file (\"a b\" per line): run on that mesh instead of mesh_converge()")
     ap.add_argument("--node", choices=("rust", "go", "nim"), default="rust")
     ap.add_argument("--publisher-id", type=int, help="run.sh publisher_id (when the log cannot name one)")
     ap.add_argument("--rotation", type=int, default=0, help="run.sh publisher_rotation")

@@ -447,6 +447,33 @@ gs_status gs_mesh_converge(struct gs_ctx* ctx, uint32_t max_heartbeats, uint32_t
  * count[peers]. Either pointer may be NULL. */
 gs_status gs_get_mesh(struct gs_ctx* ctx, uint32_t* mesh, uint8_t* count);
 
+/* A caller's mesh in place of the converged one (DESIGN.md §2.3 "A caller's mesh"):
+ * the mesh a real run ended up with (a tracer's Graft / Prune events,
+ * go-test-node/metrics.go:328-340), or any what-if mesh, the empty one included. Either
+ * call stands where gs_mesh_converge stands: it needs the topology and the links
+ * (GS_ESTATE), leaves what a converge would leave (the mesh bit of gs_get_csr's flags
+ * on exactly these links, rows ascending, no back-offs), and is undone by whatever
+ * undoes a converged mesh; a later gs_mesh_converge starts from the empty mesh as
+ * always. The mesh is a function of the set of links: no order of rows' slots or of the
+ * list shows in it. GS_EUNSUPPORTED when churn_ppm != 0 (every epoch's mesh then
+ * comes from the chain, which starts at epoch 0). A refused mesh (GS_EINVAL for a
+ * defect, GS_ERANGE for a row wider than GS_MESH_W) leaves the context as it was;
+ * gs_last_error names the kind of defect and the smallest slot, link, peer or CSR
+ * entry that has it. The mesh events of gs_set_mesh_events describe a converge:
+ * their getters return GS_ESTATE until the next one. Partitioned runs need the
+ * import in every context or in none (GS_EINVAL before any batch otherwise).
+ * gs_set_mesh: gs_get_mesh's layout, mesh[peers*GS_MESH_W] of plain ids in any order
+ * inside a row; a row is its first count[u] slots, or with count == NULL ends at its
+ * first UINT32_MAX. Every link needs its reverse in the other peer's row. */
+gs_status gs_set_mesh(struct gs_ctx* ctx, const uint32_t* mesh, const uint8_t* count);
+/* gs_set_mesh_links: the undirected links {a[i], b[i]}, in any order and either
+ * orientation, each once. n_links == 0 is the empty mesh (flood publishing plus
+ * gossip only). */
+gs_status gs_set_mesh_links(struct gs_ctx* ctx, uint64_t n_links, const uint32_t* a, const uint32_t* b);
+/* Host only. One "a b" line per link with a < b, in row order: the text form of
+ * gs_write_dials, read back by gs_read_dials. count may be NULL as for gs_set_mesh. */
+gs_status gs_write_mesh_links(const char* path, uint32_t peers, const uint32_t* mesh, const uint8_t* count);
+
 /* Simulate n_msgs publishes (replaces publish_new_message + the receive /
  * forward / reassembly loop, main.rs:79-143,519-528). Results go to `sink`
  * (may be NULL: device-resident run, counters only). */

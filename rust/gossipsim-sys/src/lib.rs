@@ -140,6 +140,9 @@ extern "C" {
     pub fn gs_graph_info(ctx: *const gs_ctx, peers: *mut u32, nnz: *mut u64, max_deg: *mut u32) -> gs_status;
     pub fn gs_get_csr(ctx: *mut gs_ctx, row_ptr: *mut u64, col: *mut u32, flags: *mut u8) -> gs_status;
     pub fn gs_mesh_converge(ctx: *mut gs_ctx, max_heartbeats: u32, epochs: *mut u32) -> gs_status;
+    pub fn gs_set_mesh(ctx: *mut gs_ctx, mesh: *const u32, count: *const u8) -> gs_status;
+    pub fn gs_set_mesh_links(ctx: *mut gs_ctx, n_links: u64, a: *const u32, b: *const u32) -> gs_status;
+    pub fn gs_write_mesh_links(path: *const c_char, peers: u32, mesh: *const u32, count: *const u8) -> gs_status;
     pub fn gs_get_mesh(ctx: *mut gs_ctx, mesh: *mut u32, count: *mut u8) -> gs_status;
     pub fn gs_run(ctx: *mut gs_ctx, sched: *const gs_publish, n: u64, sink: *const gs_result_sink) -> gs_status;
     pub fn gs_run_log(ctx: *mut gs_ctx, sched: *const gs_publish, n: u64, on_text: gs_text_fn, user: *mut c_void,
