@@ -189,6 +189,7 @@ extern "C" gs_status gs_build_topology(gs_ctx* ctx) {
   ctx->cell_valid = false;
   ctx->mesh_built = false;
   ctx->glp_prefer = false;
+  ctx->ld_ready = false;  // link deliveries: the edge slots mean other links
   if (ctx->topo_fp) graph_replaced(*ctx);  // the graph before was an imported one, another than this
   ctx->topo_fp = 0;
   GS_API_END(ctx)
@@ -374,6 +375,7 @@ extern "C" gs_status gs_reset_stats(gs_ctx* ctx) {
   if (ctx->traffic)
     GS_HIP(hipMemsetAsync(ctx->d_traffic.p, 0, (size_t)ctx->cfg.peers * GS_TRAFFIC_COLS * 8, ctx->stream));
   pubsub_reset(*ctx);
+  linkdel_reset(*ctx);
   GS_HIP(hipStreamSynchronize(ctx->stream));
   memset(&ctx->stats, 0, sizeof(ctx->stats));
   // (glp_prefer, the path choice learnt from a failed no-op proof, is no statistic: it
@@ -472,6 +474,42 @@ extern "C" gs_status gs_get_mesh_series(gs_ctx* ctx, uint64_t* out, uint32_t row
   if ((size_t)rows * GS_MESH_SERIES_COLS != ctx->me_series.size())
     ctx->fail(GS_EINVAL, "gs_get_mesh_series: rows is not gs_mesh_series_rows' count");
   std::copy(ctx->me_series.begin(), ctx->me_series.end(), out);
+  GS_API_END(ctx)
+}
+
+// ---- per-link first-delivery counters (gs_linkdel.h) ----
+extern "C" gs_status gs_set_link_deliveries(gs_ctx* ctx, uint32_t enable) {
+  GS_API_BEGIN(ctx)
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  linkdel_set(*ctx, enable != 0);
+  GS_API_END(ctx)
+}
+
+static void linkdel_state(gs_ctx* ctx, const void* out) {
+  if (!out) ctx->fail(GS_EINVAL, "null link delivery array");
+  if (!ctx->linkdel) ctx->fail(GS_ESTATE, "gs_set_link_deliveries(ctx, 1) first");
+  if (!ctx->topo_built) ctx->fail(GS_ESTATE, "gs_build_topology first");
+}
+
+extern "C" gs_status gs_get_link_deliveries(gs_ctx* ctx, uint64_t* out) {
+  GS_API_BEGIN(ctx)
+  linkdel_state(ctx, out);
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  linkdel_get(*ctx, out);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_get_peer_given(gs_ctx* ctx, uint64_t* out) {
+  GS_API_BEGIN(ctx)
+  linkdel_state(ctx, out);
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  linkdel_given(*ctx, out);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_reset_link_deliveries(gs_ctx* ctx) {
+  GS_API_BEGIN(ctx)
+  linkdel_reset(*ctx);
   GS_API_END(ctx)
 }
 

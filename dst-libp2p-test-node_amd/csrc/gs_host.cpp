@@ -666,6 +666,26 @@ extern "C" gs_status gs_write_dials(const char* path, uint32_t peers, const uint
   return (fclose(f) != 0 || bad) ? GS_EINVAL : GS_OK;
 }
 
+// One "receiver sender publish mesh gossip" line per CSR entry with a non-zero count, in CSR
+// order (gs_get_link_deliveries' counts beside gs_get_csr's arrays).
+extern "C" gs_status gs_write_link_deliveries(const char* path, uint32_t peers, const uint64_t* row_ptr,
+                                              const uint32_t* col, const uint64_t* counts) {
+  if (!path || !row_ptr || (row_ptr[peers] && (!col || !counts))) return GS_EINVAL;
+  FILE* f = fopen(path, "w");
+  if (!f) return GS_EINVAL;
+  std::vector<char> buf(1 << 20);
+  setvbuf(f, buf.data(), _IOFBF, buf.size());
+  for (uint32_t u = 0; u < peers; u++)
+    for (uint64_t e = row_ptr[u]; e < row_ptr[u + 1]; e++) {
+      const uint64_t* r = counts + e * GS_LD_COLS;
+      if (r[GS_LD_PUBLISH] | r[GS_LD_MESH] | r[GS_LD_GOSSIP])
+        fprintf(f, "%u %u %llu %llu %llu\n", u, col[e], (unsigned long long)r[GS_LD_PUBLISH],
+                (unsigned long long)r[GS_LD_MESH], (unsigned long long)r[GS_LD_GOSSIP]);
+    }
+  const bool bad = ferror(f) != 0;
+  return (fclose(f) != 0 || bad) ? GS_EINVAL : GS_OK;
+}
+
 // One "a b" line per mesh link with a < b, in row order (gs_get_mesh's layout; a row is its first
 // count[u] slots, at most GS_MESH_W, or ends at its first UINT32_MAX): gs_read_dials reads it back.
 extern "C" gs_status gs_write_mesh_links(const char* path, uint32_t peers, const uint32_t* mesh, const uint8_t* count) {

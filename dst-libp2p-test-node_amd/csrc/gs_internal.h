@@ -60,8 +60,10 @@ inline long env_int(const char* name, long dflt) {
 // fell outside the K-window ring the host bound promised. Both re-run the batch on k_pull.
 // ERR_LAT16: a logged latency of 65535 ms or more for the u16 stream (GS_WANT_LAT_MS).
 // ERR_LINES: a peer's line counter of the arrival log's text would pass 2^32 - 1 in the batch (k_lt_room).
+// ERR_LINK: a final key's src is not in the receiver's CSR row (k_linkdel, gs_linkdel.h).
 enum : uint32_t {
-  ERR_TIME = 1, ERR_HOPS = 2, ERR_MESH = 4, ERR_DEG = 8, ERR_LIST = 16, ERR_RING = 32, ERR_LAT16 = 64, ERR_LINES = 128
+  ERR_TIME = 1, ERR_HOPS = 2, ERR_MESH = 4, ERR_DEG = 8, ERR_LIST = 16, ERR_RING = 32, ERR_LAT16 = 64, ERR_LINES = 128,
+  ERR_LINK = 256
 };
 
 // Device buffer owned by a context.
@@ -150,9 +152,13 @@ struct Ctx {
   DevBuf<uint64_t> d_traffic;  // [N][GS_TRAFFIC_COLS]
   bool pubsub = false;         // gs_set_pubsub_counts (gs_pubsub.h): per-peer event counters
   DevBuf<uint64_t> d_pubsub;   // [N][GS_PUBSUB_COLS]
-  // A pass over the finished batch's dense final keys follows (either switch): the run plan
+  // gs_set_link_deliveries (gs_linkdel.h): per-link first-delivery counters, aligned with the CSR
+  bool linkdel = false;
+  bool ld_ready = false;        // d_linkdel is allocated for the current graph and zeroed since the last reset
+  DevBuf<uint64_t> d_linkdel;   // [nnz][GS_LD_COLS]
+  // A pass over the finished batch's dense final keys follows (any of the switches): the run plan
   // keeps dense rows and the churn ring's ELL snapshots, and takes no path without them.
-  bool keys_pass() const { return traffic || pubsub; }
+  bool keys_pass() const { return traffic || pubsub || linkdel; }
   // gs_set_peer_delay (gs_peerdelay.h): per-peer delay accumulators of the context's own rows
   bool pdelay = false;
   DevBuf<uint64_t> d_pdelay;   // [PD_COLS][own rows]
@@ -491,6 +497,11 @@ void log_text_reset(Ctx& c);
 void pubsub_set(Ctx& c, bool on);
 void pubsub_reset(Ctx& c);
 void pubsub_get(Ctx& c, uint64_t* out);
+// per-link first-delivery counters (gs_linkdel.h)
+void linkdel_set(Ctx& c, bool on);
+void linkdel_reset(Ctx& c);
+void linkdel_get(Ctx& c, uint64_t* out);
+void linkdel_given(Ctx& c, uint64_t* out);
 // mesh event counts of the last converge (gs_meshev.h, gs_mesh.hip)
 void mesh_events_set(Ctx& c, bool on);
 void mesh_events_get(Ctx& c, uint64_t* out);

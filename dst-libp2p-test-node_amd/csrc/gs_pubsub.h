@@ -98,12 +98,6 @@ static void launch_pubsub(Ctx& c, const Batch& b) {
   GS_HIP(hipGetLastError());
 }
 
-// The passes over a finished batch's dense final keys (Ctx::keys_pass): each switch's own.
-static void launch_key_passes(Ctx& c, const Batch& b) {
-  if (c.traffic) launch_traffic(c, b);
-  if (c.pubsub) launch_pubsub(c, b);
-}
-
 static void pubsub_zero(Ctx& c) {
   GS_HIP(hipMemsetAsync(c.d_pubsub.p, 0, (size_t)c.cfg.peers * GS_PUBSUB_COLS * 8, c.stream));
 }

@@ -933,6 +933,7 @@ static void launch_traffic(Ctx& c, const Batch& b) {
 }
 
 #include "gs_pubsub.h"
+#include "gs_linkdel.h"
 
 // Read the device counters into ctx->stats (and raise the device error word).
 static void collect_stats(Ctx& c) {
@@ -942,6 +943,7 @@ static void collect_stats(Ctx& c) {
   const uint64_t* h = c.h_pinned;
   if (h[C_ERR] & ERR_TIME) c.fail(GS_ERANGE, "relative arrival time overflowed the key's time field");
   if (h[C_ERR] & ERR_HOPS) c.fail(GS_ERANGE, "hop count overflowed the key's 6-bit hop field");
+  if (h[C_ERR] & ERR_LINK) c.fail(GS_ERANGE, "a final key names a sender outside the receiver's CSR row (link deliveries)");
   c.stats.frag_deliveries = h[C_FD];
   c.stats.relaxations = h[C_R] + h[C_R_FWD] + h[C_GOSSIP];
   c.stats.gossip_iwant = h[C_GOSSIP];

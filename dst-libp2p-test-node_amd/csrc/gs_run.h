@@ -97,7 +97,7 @@ static Batch with_window(const Batch& b, uint64_t w) {
 }
 
 // Dense rows: a sink's rows or summaries, a pass over the final keys (Ctx::keys_pass:
-// per-peer traffic or pubsub counts), GS_LPULL_DENSE (diagnostic:
+// per-peer traffic, pubsub counts or per-link first deliveries), GS_LPULL_DENSE (diagnostic:
 // dense rows + k_complete, whose known key stream calibrates the PMC read factor,
 // scripts/pmc_summary.py). IDONTWANT batches keep their final keys dense all along
 // and ask for no conversion: run_lpull_batch never looks at `dense` under IDONTWANT, so

@@ -448,6 +448,7 @@ void graph_replaced(Ctx& c) {
   c.ring_lo = 1;
   c.ring_hi = 0;
   c.meshev_valid = false;
+  c.ld_ready = false;  // the edge slots mean other links
 }
 
 // ---- import: everything is built in buffers of the call's own and swapped

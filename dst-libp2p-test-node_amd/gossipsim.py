@@ -137,6 +137,11 @@ SIGNATURES = {
     "gs_get_pubsub_counts": (i32, [ctypes.c_void_p, P(u64)]),
     "gs_reset_pubsub_counts": (i32, [ctypes.c_void_p]),
     "gs_write_pubsub_metrics": (i32, [P(GsConfig), ctypes.c_char_p, u32, P(u64)]),
+    "gs_set_link_deliveries": (i32, [ctypes.c_void_p, u32]),
+    "gs_get_link_deliveries": (i32, [ctypes.c_void_p, P(u64)]),
+    "gs_get_peer_given": (i32, [ctypes.c_void_p, P(u64)]),
+    "gs_reset_link_deliveries": (i32, [ctypes.c_void_p]),
+    "gs_write_link_deliveries": (i32, [ctypes.c_char_p, u32, P(u64), P(u32), P(u64)]),
     "gs_set_mesh_events": (i32, [ctypes.c_void_p, u32]),
     "gs_get_mesh_events": (i32, [ctypes.c_void_p, P(u64)]),
     "gs_mesh_series_rows": (i32, [ctypes.c_void_p, P(u32)]),
@@ -335,6 +340,29 @@ def write_mesh_series(path, series):
     rc = lib().gs_write_mesh_series(path.encode(), _ptr(se, u64), se.shape[0])
     if rc:
         raise GossipSimError(rc, "gs_write_mesh_series failed")
+
+
+# gs_get_link_deliveries / gs_get_peer_given columns (GS_LD_*)
+LINK_DELIVERY_COLS = ("publish", "mesh", "gossip")
+
+
+def write_link_deliveries(path, row_ptr, col, counts):
+    """One "receiver sender publish mesh gossip" line per CSR entry with a non-zero count, in CSR
+    order (gs_write_link_deliveries). row_ptr, col: Simulator.csr()'s; counts: uint64
+    [nnz, len(LINK_DELIVERY_COLS)] (Simulator.link_deliveries)."""
+    row = np.ascontiguousarray(row_ptr, np.uint64)
+    c = np.ascontiguousarray(col, np.uint32)
+    ld = np.ascontiguousarray(counts, np.uint64)
+    if row.ndim != 1 or row.size < 2 or c.ndim != 1 or c.size != int(row[-1]):
+        raise GossipSimError(GS_EINVAL, "row_ptr [peers + 1] and col [row_ptr[-1]] are needed")
+    if ld.ndim != 2 or ld.shape != (c.size, len(LINK_DELIVERY_COLS)):
+        raise GossipSimError(GS_EINVAL, "counts [nnz, %d] are needed" % len(LINK_DELIVERY_COLS))
+    pad = 1 if c.size == 0 else 0  # (a pointer to take)
+    rc = lib().gs_write_link_deliveries(str(path).encode(), row.size - 1, _ptr(row, u64),
+                                        _ptr(np.resize(c, c.size + pad), u32),
+                                        _ptr(np.resize(ld.reshape(-1), ld.size + pad), u64))
+    if rc:
+        raise GossipSimError(rc, "cannot write the link deliveries %s" % path)
 
 
 def write_testnode_metrics(cfg, path, row_ptr, mesh_count, schedule, delay):
@@ -936,6 +964,34 @@ class Simulator:
         """Every peer's go-node pubsub counters and the nim node's chunk counter after runs with
         set_pubsub_counts."""
         write_pubsub_metrics(self.cfg, path, self.pubsub_counts())
+
+    # ---- per-link first deliveries (gs_set_link_deliveries, DESIGN.md §2.16) ----
+    def set_link_deliveries(self, on=True):
+        """Per-link counters of later runs: the fragments each peer received first over each of its
+        connections, split by publisher / mesh neighbour / IWANT answer (zeroed now)."""
+        self._check(lib().gs_set_link_deliveries(self.ctx, 1 if on else 0))
+
+    def link_deliveries(self):
+        """-> uint64 [nnz, len(LINK_DELIVERY_COLS)] aligned with csr(): entry e of peer u's row counts
+        what u received first from col[e]."""
+        _, nnz, _ = self.graph_info()
+        ld = np.zeros((max(nnz, 1), len(LINK_DELIVERY_COLS)), np.uint64)
+        self._check(lib().gs_get_link_deliveries(self.ctx, _ptr(ld, u64)))
+        return ld[:nnz]
+
+    def peer_given(self):
+        """-> uint64 [N, len(LINK_DELIVERY_COLS)]: the first deliveries each peer made as the sender."""
+        pg = np.zeros((self.peers, len(LINK_DELIVERY_COLS)), np.uint64)
+        self._check(lib().gs_get_peer_given(self.ctx, _ptr(pg, u64)))
+        return pg
+
+    def reset_link_deliveries(self):
+        self._check(lib().gs_reset_link_deliveries(self.ctx))
+
+    def write_link_deliveries(self, path):
+        """The non-zero link counters after runs with set_link_deliveries, one line per link."""
+        row, col, _ = self.csr()
+        write_link_deliveries(path, row, col, self.link_deliveries())
 
     # ---- what each node shows about delay (gs_set_peer_delay, DESIGN.md §2.13) ----
     def _own_rows(self):

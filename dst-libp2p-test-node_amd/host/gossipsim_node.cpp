@@ -27,7 +27,7 @@ void usage() {
           "         [--device-log]\n"
           "         [--gml network_topology.gml --yaml shadow.yaml] [--schedule FILE] [--shadowlog PATH] [--metrics PATH]\n"
           "         [--testnode-metrics PATH] [--pubsub-metrics PATH] [--mesh-metrics PATH] [--mesh-series PATH]\n"
-          "         [--topology DIALS] [--dump-topology PATH] [--mesh LINKS] [--dump-mesh PATH]\n"
+          "         [--topology DIALS] [--dump-topology PATH] [--mesh LINKS] [--dump-mesh PATH] [--link-deliveries PATH]\n"
           "  --topology imports a dial list (one \"dialer target\" per line) in place of the random dialing;\n"
           "    --dump-topology writes the dial list of the graph the run used\n"
           "  --mesh imports a mesh (one \"a b\" link per line) in place of the heartbeats' converge (not with\n"
@@ -40,6 +40,8 @@ void usage() {
           "  --pubsub-metrics writes the go node's per-peer pubsub counters (libp2p_pubsub_*, gs_set_pubsub_counts)\n"
           "  --mesh-metrics writes the go node's per-peer GRAFT / PRUNE counters and mesh gauges, --mesh-series the\n"
           "    per-epoch mesh health as CSV, both of the mesh convergence (gs_set_mesh_events)\n"
+          "  --link-deliveries writes \"receiver sender publish mesh gossip\" per connection that delivered a fragment\n"
+          "    first: who delivered to whom, by the publisher, over the mesh, by IWANT answers (gs_set_link_deliveries)\n"
           "env: PEERS CONNECTTO FRAGMENTS MUXER MAXCONNECTIONS GOSSIPSUB_* SELFTRIGGER GS_NODE GS_SEED GS_BATCH\n"
           "     GS_DEVICE\n");
 }
@@ -127,7 +129,7 @@ int main(int argc, char** argv) {
   // after the injector sends it (topogen.py:64-69); tx_time is stamped then
   uint64_t http_us = 3000;
   std::string latencies, gml, yaml, shadowlog, metrics, schedule, testnode, pubsub, mesh_metrics, mesh_series;
-  std::string topology, dump_topology, mesh_file, dump_mesh;
+  std::string topology, dump_topology, mesh_file, dump_mesh, link_deliveries;
   bool set_size = false, set_msgs = false, set_delay = false, set_t0 = false, device_log = false;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -163,6 +165,7 @@ int main(int argc, char** argv) {
     else if (a == "--dump-topology") dump_topology = next();  // the dial list of the graph the run used
     else if (a == "--mesh") mesh_file = next();  // a link list ("a b" per line) in place of the converge
     else if (a == "--dump-mesh") dump_mesh = next();  // the links of the mesh the run used
+    else if (a == "--link-deliveries") link_deliveries = next();  // per-link first deliveries (P2, main.rs:252-258)
     else if (a == "--schedule") schedule = next();  // rows: t_pub_ns publisher msg_size [frags]
     else { usage(); return 2; }
   }
@@ -211,6 +214,8 @@ int main(int argc, char** argv) {
   if (counters && (st = gs_set_traffic(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_traffic");
   if (!testnode.empty() && (st = gs_set_peer_delay(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_peer_delay");
   if (!pubsub.empty() && (st = gs_set_pubsub_counts(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_pubsub_counts");
+  if (!link_deliveries.empty() && (st = gs_set_link_deliveries(ctx, 1)) != GS_OK)
+    return die(ctx, st, "gs_set_link_deliveries");
   const bool mesh_events = !mesh_metrics.empty() || !mesh_series.empty();
   if (mesh_events && (st = gs_set_mesh_events(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_mesh_events");
   if (topology.empty()) {
@@ -326,7 +331,7 @@ int main(int argc, char** argv) {
     strm.hist_ms.clear();
     if (!latencies.empty() && (st = gs_log_open(&cfg, latencies.c_str(), &strm.log)) != GS_OK)
       return die(ctx, st, "gs_log_open");
-    gs_reset_stats(ctx);  // (also restarts the per-peer traffic and pubsub counters)
+    gs_reset_stats(ctx);  // (also restarts the per-peer traffic and pubsub counters and the link deliveries)
     gs_result_sink wide{};
     wide.want = GS_WANT_T_COMPLETE;
     wide.on_block = on_block;
@@ -386,6 +391,16 @@ int main(int argc, char** argv) {
     if ((st = gs_get_pubsub_counts(ctx, pc.data())) != GS_OK) return die(ctx, st, "gs_get_pubsub_counts");
     if ((st = gs_write_pubsub_metrics(&cfg, pubsub.c_str(), cfg.peers, pc.data())) != GS_OK)
       return die(ctx, st, "gs_write_pubsub_metrics");
+  }
+  if (!link_deliveries.empty()) {
+    uint64_t nnz = 0;
+    if ((st = gs_graph_info(ctx, nullptr, &nnz, nullptr)) != GS_OK) return die(ctx, st, "gs_graph_info");
+    std::vector<uint64_t> row((size_t)cfg.peers + 1), ld((nnz + 1) * GS_LD_COLS);
+    std::vector<uint32_t> col(nnz + 1);
+    if ((st = gs_get_csr(ctx, row.data(), col.data(), nullptr)) != GS_OK) return die(ctx, st, "gs_get_csr");
+    if ((st = gs_get_link_deliveries(ctx, ld.data())) != GS_OK) return die(ctx, st, "gs_get_link_deliveries");
+    if ((st = gs_write_link_deliveries(link_deliveries.c_str(), cfg.peers, row.data(), col.data(), ld.data())) != GS_OK)
+      return die(ctx, st, "gs_write_link_deliveries");
   }
   gs_destroy(ctx);
   return 0;

@@ -571,6 +571,45 @@ gs_status gs_reset_pubsub_counts(struct gs_ctx* ctx);
  * (gs_get_pubsub_counts). Host only. */
 gs_status gs_write_pubsub_metrics(const gs_config* cfg, const char* path, uint32_t peers, const uint64_t* counts);
 
+/* ---- per-link first-delivery counts -------------------------
+ * Of the fragments a peer received first, how many came over each of its
+ * connections: the per-link question of the one scoring term all three nodes
+ * configure, first-message-deliveries P2 (rust-test-node/src/main.rs:252-258,
+ * go-test-node/main.go:186-193, nim-test-node/gossipsub-queues/main.nim:335-340).
+ * The sender is the src field of the final key. A first receipt
+ * is GS_PS_FIRST's: a fragment's first arrival at a non-publisher. */
+enum { GS_LD_PUBLISH = 0,   /* the sender is the message's publisher (with or without flood-publish) */
+       GS_LD_MESH = 1,      /* the sender is in the receiver's row of the frozen mesh               */
+       GS_LD_GOSSIP = 2,    /* neither: an IWANT answer                            */
+       GS_LD_COLS = 3 };
+/* 1: every finished batch of gs_run and gs_run_log adds its first receipts to
+ * per-link counters on the device, [nnz][GS_LD_COLS] aligned with gs_get_csr's
+ * arrays: entry e in the row of peer u counts the fragments u received first
+ * from col[e]; a peer's row over the three columns sums to its GS_PS_FIRST. One
+ * extra pass over the final keys (off by default, diagnostic). Enabling zeroes
+ * the counters; it may come before a graph exists (they are allocated when first
+ * needed). They carry across batches and calls and are zeroed by
+ * gs_reset_link_deliveries, gs_reset_stats, and a graph built or imported
+ * (gs_build_topology, gs_set_topology, gs_set_topology_dials: the entries then
+ * mean other links). GS_EUNSUPPORTED on a context with churn_ppm > 0 (the mesh
+ * of a send and of its arrival can differ). Partitioned mode (gs_part_begin,
+ * gs_run_partitioned*) returns GS_EUNSUPPORTED while the switch is on.
+ * gs_save_state does not carry the counters: a loaded context has the switch
+ * off. */
+gs_status gs_set_link_deliveries(struct gs_ctx* ctx, uint32_t enable);
+/* out[nnz][GS_LD_COLS]. GS_ESTATE while the switch is off or no graph exists. */
+gs_status gs_get_link_deliveries(struct gs_ctx* ctx, uint64_t* out);
+/* out[peers][GS_LD_COLS]: the first deliveries each peer made as the sender, the
+ * transposed sum of the link counters (what P2 rewards), derived on the device
+ * at read-out. GS_ESTATE as gs_get_link_deliveries. */
+gs_status gs_get_peer_given(struct gs_ctx* ctx, uint64_t* out);
+gs_status gs_reset_link_deliveries(struct gs_ctx* ctx);
+/* Host only. One line "receiver sender publish mesh gossip" (plain integers) per
+ * CSR entry with a non-zero count, in CSR order; row_ptr[peers+1], col[nnz] and
+ * counts[nnz][GS_LD_COLS] are host copies (gs_get_csr, gs_get_link_deliveries). */
+gs_status gs_write_link_deliveries(const char* path, uint32_t peers, const uint64_t* row_ptr, const uint32_t* col,
+                                   const uint64_t* counts);
+
 /* ---- mesh events and per-epoch mesh health -----------------
  * What go-test-node/metrics.go:164-190 counts per node (GRAFT and PRUNE RPCs
  * sent and received) and what its tracer follows (metrics.go:224-258 mesh size,
@@ -808,8 +847,9 @@ gs_status gs_comm_destroy(gs_comm* comm);
  * the batch's messages for all peers, one all-to-all hands every part its own
  * peers' rows; gs_stats.ms_batches counts them). Collective over the
  * communicator. Results are bit-identical to gs_run. GS_EUNSUPPORTED: per-peer
- * traffic (gs_set_traffic), per-peer pubsub counts (gs_set_pubsub_counts), and
- * sink summaries of a message-sharded batch.
+ * traffic (gs_set_traffic), per-peer pubsub counts (gs_set_pubsub_counts),
+ * per-link first deliveries (gs_set_link_deliveries), and sink summaries of a
+ * message-sharded batch.
  * Every sinks[i] follows gs_result_sink's rules (GS_EINVAL otherwise); on_lat
  * receives [n][own peers] u16, and the parts' blocks side by side are gs_run's
  * on_lat stream. GS_ERANGE (a logged latency of 65535 ms or more): no part, and
