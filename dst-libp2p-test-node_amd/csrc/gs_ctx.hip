@@ -313,6 +313,7 @@ extern "C" gs_status gs_run(gs_ctx* ctx, const gs_publish* sched, uint64_t n_msg
   if (ctx->pdelay && ctx->part_parts > 1)  // (the accumulators cover the partition's rows, gs_run all peers)
     ctx->fail(GS_EUNSUPPORTED, "gs_run with gs_set_peer_delay on a partitioned context: use gs_run_partitioned");
   GS_HIP(hipSetDevice(ctx->cfg.device));
+  msgcost_begin(*ctx, n_msgs);
   if (n_msgs) run_messages(*ctx, sched, n_msgs, sink);
   GS_API_END(ctx)
 }
@@ -334,6 +335,7 @@ extern "C" gs_status gs_run_log(gs_ctx* ctx, const gs_publish* sched, uint64_t n
   gs_result_sink sink{};
   sink.want = GS_WANT_LAT_MS;
   sink.on_lat = text_sink_unused;
+  msgcost_begin(*ctx, n_msgs);
   if (n_msgs) run_messages(*ctx, sched, n_msgs, &sink);
   GS_API_END(ctx)
 }
@@ -510,6 +512,31 @@ extern "C" gs_status gs_get_peer_given(gs_ctx* ctx, uint64_t* out) {
 extern "C" gs_status gs_reset_link_deliveries(gs_ctx* ctx) {
   GS_API_BEGIN(ctx)
   linkdel_reset(*ctx);
+  GS_API_END(ctx)
+}
+
+// ---- per-message cost table of the last gs_run / gs_run_log call (gs_msgcost.h) ----
+extern "C" gs_status gs_set_message_costs(gs_ctx* ctx, uint32_t enable) {
+  GS_API_BEGIN(ctx)
+  msgcost_set(*ctx, enable != 0);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_message_costs_rows(gs_ctx* ctx, uint64_t* rows) {
+  GS_API_BEGIN(ctx)
+  if (!rows) ctx->fail(GS_EINVAL, "null rows");
+  if (!ctx->msgcost) ctx->fail(GS_ESTATE, "gs_set_message_costs(ctx, 1) first");
+  *rows = ctx->mc_rows;
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_get_message_costs(gs_ctx* ctx, uint64_t* out, uint64_t rows) {
+  GS_API_BEGIN(ctx)
+  if (!ctx->msgcost) ctx->fail(GS_ESTATE, "gs_set_message_costs(ctx, 1) first");
+  if (rows != ctx->mc_rows) ctx->fail(GS_EINVAL, "gs_get_message_costs: rows is not gs_message_costs_rows' count");
+  if (!out && rows) ctx->fail(GS_EINVAL, "null message costs array");
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  msgcost_get(*ctx, out);
   GS_API_END(ctx)
 }
 

@@ -686,6 +686,53 @@ extern "C" gs_status gs_write_link_deliveries(const char* path, uint32_t peers, 
   return (fclose(f) != 0 || bad) ? GS_EINVAL : GS_OK;
 }
 
+// One TSV line per message: the schedule fields, the counts (gs_get_message_costs) and the
+// wire cost they imply. The cost is linear in the counts: every fragment copy of message i is
+// W_i bytes in pk_i packets, every IHAVE / IWANT one control RPC, and every arrival is
+// answered by ceil(packets / 2) pure ACKs — the sum over peers of the per-peer traffic
+// (gs_get_traffic) of that message alone.
+extern "C" gs_status gs_write_message_costs(const gs_config* cfg, const char* path, const gs_publish* sched,
+                                            uint64_t n_msgs, const uint64_t* costs) {
+  if (!cfg || !path || (n_msgs && (!sched || !costs))) return GS_EINVAL;
+  if (cfg->muxer > GS_MUX_MPLEX || cfg->node > GS_NODE_NIM) return GS_EINVAL;
+  for (uint64_t i = 0; i < n_msgs; i++) {
+    const uint32_t F = sched[i].frags ? sched[i].frags : cfg->fragments;
+    if (!F || gs::frag_invalid(cfg->node, sched[i].msg_size, F)) return GS_EINVAL;
+  }
+  uint64_t ih[3], iw[3], ack = 0;
+  gs_control_packets(GS_CTRL_IHAVE, cfg->node, cfg->muxer, &ih[0], &ih[1], &ih[2]);
+  gs_control_packets(GS_CTRL_IWANT, cfg->node, cfg->muxer, &iw[0], &iw[1], &iw[2]);
+  gs_control_packets(GS_CTRL_ACK, cfg->node, cfg->muxer, &ack, nullptr, nullptr);
+  FILE* f = fopen(path, "w");
+  if (!f) return GS_EINVAL;
+  std::vector<char> buf(1 << 20);
+  setvbuf(f, buf.data(), _IOFBF, buf.size());
+  fprintf(f, "#msg\tt_pub_ns\tpublisher\tmsg_size\tchunks\tdata_tx\tdata_rx\tfirst\tdup\tihave_tx\tihave_rx\tiwant\t"
+             "delivered\ttx_bytes\trx_bytes\ttx_packets\trx_packets\tack_packets\tack_bytes\n");
+  typedef unsigned long long ull;
+  for (uint64_t i = 0; i < n_msgs; i++) {
+    const gs_publish& s = sched[i];
+    const uint64_t* r = costs + i * GS_MC_COLS;
+    const uint32_t F = s.frags ? s.frags : cfg->fragments;
+    const uint64_t payload = gs::frag_payload(cfg->node, s.msg_size, F);
+    uint64_t pk = 0, hd = 0;
+    const uint64_t W = gs_wire_bytes(payload, cfg->muxer, cfg->signed_msgs);
+    gs_wire_packets(payload, cfg->muxer, cfg->signed_msgs, &pk, &hd);
+    const uint64_t txb = r[GS_MC_DATA_TX] * W + r[GS_MC_IHAVE_TX] * ih[0] + r[GS_MC_IWANT] * iw[0];
+    const uint64_t rxb = r[GS_MC_DATA_RX] * W + r[GS_MC_IHAVE_RX] * ih[0] + r[GS_MC_IWANT] * iw[0];
+    const uint64_t txp = r[GS_MC_DATA_TX] * pk + r[GS_MC_IHAVE_TX] * ih[1] + r[GS_MC_IWANT] * iw[1];
+    const uint64_t rxp = r[GS_MC_DATA_RX] * pk + r[GS_MC_IHAVE_RX] * ih[1] + r[GS_MC_IWANT] * iw[1];
+    const uint64_t acks = r[GS_MC_DATA_RX] * ((pk + 1) / 2) + r[GS_MC_IHAVE_RX] * ((ih[1] + 1) / 2) +
+                          r[GS_MC_IWANT] * ((iw[1] + 1) / 2);
+    fprintf(f, "%llu\t%llu\t%u\t%u\t%u", (ull)i, (ull)s.t_pub_ns, s.publisher, s.msg_size, F);
+    for (int k = 0; k < GS_MC_COLS; k++) fprintf(f, "\t%llu", (ull)r[k]);
+    fprintf(f, "\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (ull)txb, (ull)rxb, (ull)txp, (ull)rxp, (ull)acks,
+            (ull)(acks * ack));
+  }
+  const bool bad = ferror(f) != 0;
+  return (fclose(f) != 0 || bad) ? GS_EINVAL : GS_OK;
+}
+
 // One "a b" line per mesh link with a < b, in row order (gs_get_mesh's layout; a row is its first
 // count[u] slots, at most GS_MESH_W, or ends at its first UINT32_MAX): gs_read_dials reads it back.
 extern "C" gs_status gs_write_mesh_links(const char* path, uint32_t peers, const uint32_t* mesh, const uint8_t* count) {

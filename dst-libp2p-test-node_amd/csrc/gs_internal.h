@@ -158,7 +158,12 @@ struct Ctx {
   DevBuf<uint64_t> d_linkdel;   // [nnz][GS_LD_COLS]
   // A pass over the finished batch's dense final keys follows (any of the switches): the run plan
   // keeps dense rows and the churn ring's ELL snapshots, and takes no path without them.
-  bool keys_pass() const { return traffic || pubsub || linkdel; }
+  bool keys_pass() const { return traffic || pubsub || linkdel || msgcost; }
+  // gs_set_message_costs (gs_msgcost.h): the per-message cost table of the last gs_run / gs_run_log call
+  bool msgcost = false;
+  uint64_t mc_rows = 0;            // the call's messages (0 before a run and after enabling)
+  DevBuf<uint64_t> d_msgcost;      // [mc_rows][GS_MC_COLS], rows in the order the run driver took the messages
+  std::vector<uint64_t> mc_perm;   // row i is the schedule's message mc_perm[i] (class_plan); empty: row i is message i
   // gs_set_peer_delay (gs_peerdelay.h): per-peer delay accumulators of the context's own rows
   bool pdelay = false;
   DevBuf<uint64_t> d_pdelay;   // [PD_COLS][own rows]
@@ -502,6 +507,10 @@ void linkdel_set(Ctx& c, bool on);
 void linkdel_reset(Ctx& c);
 void linkdel_get(Ctx& c, uint64_t* out);
 void linkdel_given(Ctx& c, uint64_t* out);
+// per-message cost table (gs_msgcost.h)
+void msgcost_set(Ctx& c, bool on);
+void msgcost_begin(Ctx& c, uint64_t n);
+void msgcost_get(Ctx& c, uint64_t* out);
 // mesh event counts of the last converge (gs_meshev.h, gs_mesh.hip)
 void mesh_events_set(Ctx& c, bool on);
 void mesh_events_get(Ctx& c, uint64_t* out);

@@ -141,12 +141,6 @@ static void launch_linkdel(Ctx& c, const Batch& b) {
   GS_HIP(hipGetLastError());
 }
 
-// The passes over a finished batch's dense final keys (Ctx::keys_pass): each switch's own.
-static void launch_key_passes(Ctx& c, const Batch& b) {
-  if (c.traffic) launch_traffic(c, b);
-  if (c.pubsub) launch_pubsub(c, b);
-  if (c.linkdel) launch_linkdel(c, b);
-}
 
 void linkdel_set(Ctx& c, bool on) {
   if (on && c.cfg.churn_ppm)

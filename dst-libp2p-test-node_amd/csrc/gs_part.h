@@ -387,6 +387,7 @@ static uint32_t part_check(Ctx& c, const gs_publish* sched, uint64_t n_msgs) {
   if (c.traffic) c.fail(GS_EUNSUPPORTED, "per-peer traffic is not supported in partitioned mode");
   if (c.pubsub) c.fail(GS_EUNSUPPORTED, "per-peer pubsub counts (gs_set_pubsub_counts) are not supported in partitioned mode");
   if (c.linkdel) c.fail(GS_EUNSUPPORTED, "per-link first deliveries (gs_set_link_deliveries) are not supported in partitioned mode");
+  if (c.msgcost) c.fail(GS_EUNSUPPORTED, "per-message costs (gs_set_message_costs) are not supported in partitioned mode");
   if (c.cfg.idontwant && frag_payload(c.cfg.node, sched[0].msg_size, F) >= c.cfg.idontwant)
     c.fail(GS_EUNSUPPORTED, "IDONTWANT is not supported in partitioned mode");
   return F;

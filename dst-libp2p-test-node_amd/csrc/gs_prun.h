@@ -277,6 +277,7 @@ struct PRun {
     if (c.traffic) c.fail(GS_EUNSUPPORTED, "per-peer traffic is not supported in partitioned mode");
     if (c.pubsub) c.fail(GS_EUNSUPPORTED, "per-peer pubsub counts (gs_set_pubsub_counts) are not supported in partitioned mode");
     if (c.linkdel) c.fail(GS_EUNSUPPORTED, "per-link first deliveries (gs_set_link_deliveries) are not supported in partitioned mode");
+    if (c.msgcost) c.fail(GS_EUNSUPPORTED, "per-message costs (gs_set_message_costs) are not supported in partitioned mode");
     if (sinks && sinks[i].summary)
       c.fail(GS_EUNSUPPORTED, "per-message summaries of a message-sharded partitioned batch (churn, IDONTWANT or "
                               "lazy gossip IWANTs): use gs_run");

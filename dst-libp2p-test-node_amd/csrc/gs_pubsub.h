@@ -33,7 +33,7 @@ struct PeerEvents {
   __device__ void iwant_tx(const PubsubArgs&) { iwtx++; }
   __device__ void iwant_rx(const PubsubArgs&) { iwrx++; }
   __device__ void iwant_acked(const PubsubArgs&) {}
-  __device__ void flush(const PubsubArgs& t, uint32_t x) const {
+  __device__ void flush(const PubsubArgs& t, uint32_t x, uint32_t) const {
     unsigned long long* r = (unsigned long long*)(t.counts + (size_t)x * GS_PUBSUB_COLS);
     if (mtx) atomicAdd(&r[GS_PS_MSG_TX], (unsigned long long)mtx);
     if (mrx) atomicAdd(&r[GS_PS_MSG_RX], (unsigned long long)mrx);
@@ -54,12 +54,12 @@ struct PubsubAcc {
   static __device__ __forceinline__ void data_arrive(const Args& t, uint32_t x) { add(t, x, GS_PS_MSG_RX, 1); }
   static __device__ __forceinline__ void ihave_arrive(const Args& t, uint32_t x) { add(t, x, GS_PS_IHAVE_RX, 1); }
   static __device__ __forceinline__ void published(const Args&, uint32_t) {}
-  static __device__ __forceinline__ void completed(const Args&, uint32_t) {}
+  static __device__ __forceinline__ void completed(const Args&, uint32_t, uint32_t) {}
   // f: this lane's key is a first receipt (finite, not the publisher's, fl < Fe). Called by
   // every lane of the wave. Row u's lanes of the wave at `base` are [lo, hi); lane lo adds
   // the row's count.
   static __device__ __forceinline__ void first(const Args& t, bool f, bool valid, uint32_t u, uint64_t base,
-                                               uint32_t L, int lane) {
+                                               uint32_t L, int lane, uint32_t) {
     const uint64_t got = __ballot(f);
     if (!valid) return;
     const uint64_t r0 = (uint64_t)u * L, r1 = r0 + L;  // (r1 > base: the lane's gid is in [r0, r1))

@@ -934,6 +934,16 @@ static void launch_traffic(Ctx& c, const Batch& b) {
 
 #include "gs_pubsub.h"
 #include "gs_linkdel.h"
+#include "gs_msgcost.h"
+
+// The passes over a finished batch's dense final keys (Ctx::keys_pass): each switch's own.
+// i0: the batch's first message in the run driver's schedule.
+static void launch_key_passes(Ctx& c, const Batch& b, uint64_t i0) {
+  if (c.traffic) launch_traffic(c, b);
+  if (c.pubsub) launch_pubsub(c, b);
+  if (c.linkdel) launch_linkdel(c, b);
+  if (c.msgcost) launch_msgcost(c, b, i0);
+}
 
 // Read the device counters into ctx->stats (and raise the device error word).
 static void collect_stats(Ctx& c) {
@@ -1701,6 +1711,7 @@ void run_messages(Ctx& c, const gs_publish* sched, uint64_t n_msgs, const gs_res
   std::vector<uint64_t> perm;
   std::vector<uint8_t> cut;
   if (!class_plan(c, sched, n_msgs, sink, perm, cut)) return Run(c, sched, n_msgs, sink, nullptr).run();
+  if (c.msgcost) c.mc_perm = perm;  // the cost table's rows come in class order (msgcost_get)
   std::vector<gs_publish> ps(n_msgs);
   for (uint64_t i = 0; i < n_msgs; i++) ps[i] = sched[perm[i]];
   if (!sink) return Run(c, ps.data(), n_msgs, nullptr, &cut).run();

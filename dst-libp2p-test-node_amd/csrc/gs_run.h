@@ -97,7 +97,7 @@ static Batch with_window(const Batch& b, uint64_t w) {
 }
 
 // Dense rows: a sink's rows or summaries, a pass over the final keys (Ctx::keys_pass:
-// per-peer traffic, pubsub counts or per-link first deliveries), GS_LPULL_DENSE (diagnostic:
+// per-peer traffic, pubsub counts, per-link first deliveries or message costs), GS_LPULL_DENSE (diagnostic:
 // dense rows + k_complete, whose known key stream calibrates the PMC read factor,
 // scripts/pmc_summary.py). IDONTWANT batches keep their final keys dense all along
 // and ask for no conversion: run_lpull_batch never looks at `dense` under IDONTWANT, so
@@ -950,7 +950,7 @@ struct Run {
   }
 
   void complete(const BatchRun& r) {
-    if (c.keys_pass()) launch_key_passes(c, r.b);
+    if (c.keys_pass()) launch_key_passes(c, r.b, r.i0);
     launch_complete(c, r.b, 0, N, sink, r.i0);
   }
 
@@ -1152,7 +1152,7 @@ struct Run {
 
   // Without lazy gossip the eager result is the batch's.
   bool finish_eager(const BatchRun& r) {
-    if (c.keys_pass()) launch_key_passes(c, r.b);
+    if (c.keys_pass()) launch_key_passes(c, r.b, r.i0);
     if (!r.nl.on) launch_complete(c, r.b, 0, N, sink, r.i0);  // (a no-log batch: the passes completed it)
     return true;
   }
@@ -1180,7 +1180,7 @@ struct Run {
       noop = bsum ? ms[0] == (uint64_t)B * (N - 1) && ms[1] < rel0[0] + b.lat_min : gossip_noop(b, ms.data(), rel0);
     }
     if (noop) {
-      if (c.keys_pass()) launch_key_passes(c, b);
+      if (c.keys_pass()) launch_key_passes(c, b, r.i0);
       deliver(c, b, 0, N, sink, r.i0);
       c.stats.gossip_noop_msgs += B;
       return true;

@@ -26,10 +26,10 @@
 //   P::Args   the kernel argument (Fe, flood, collide and its counters)
 //   P::Peer   one peer's counts in registers: data_tx(t, n), data_acked(t, n),
 //             data_rx(t), ihave_tx(t), ihave_acked(t), iwant_tx(t), iwant_rx(t),
-//             iwant_acked(t), flush(t, x)
+//             iwant_acked(t), flush(t, x, m)   (m: the message the lane worked for)
 //   P::data_arrive(t, x), P::ihave_arrive(t, x)   one arrival at another peer x
-//   P::published(t, p), P::completed(t, u)        (P::completions: the reassembly test runs)
-//   P::first(t, f, valid, u, base, L, lane)       the lane's own first receipt (wave-uniform call)
+//   P::published(t, p), P::completed(t, u, m)     (P::completions: the reassembly test runs)
+//   P::first(t, f, valid, u, base, L, lane, m)    the lane's own first receipt (wave-uniform call)
 // The kernels are thin __global__ wrappers, so a policy's empty hooks cost the
 // other policy's kernels nothing.
 
@@ -52,7 +52,7 @@ struct PeerTraffic {
     rxb += n * b; rxp += n * p; rxh += n * h; txc += n * ((p + 1) / 2);
   }
   __device__ void acked(uint64_t n, uint64_t p) { rxc += n * ((p + 1) / 2); }  // ACKs for n delivered sends
-  __device__ void flush(const TrafficArgs& t, uint32_t x) const {
+  __device__ void flush(const TrafficArgs& t, uint32_t x, uint32_t = 0) const {
     unsigned long long* r = (unsigned long long*)(t.traffic + (size_t)x * GS_TRAFFIC_COLS);
     const uint64_t v[GS_TRAFFIC_COLS] = {txb, rxb, txp, rxp, txh, rxh, 0, 0, txc, rxc, txc * t.ack, rxc * t.ack};
 #pragma unroll
@@ -89,8 +89,8 @@ struct TrafficAcc {
   static __device__ __forceinline__ void data_arrive(const Args& t, uint32_t x) { tr_arrive(t, x, t.W, t.pk, t.hdr); }
   static __device__ __forceinline__ void ihave_arrive(const Args& t, uint32_t x) { tr_arrive(t, x, t.ihw, t.ihpk, t.ihhd); }
   static __device__ __forceinline__ void published(const Args& t, uint32_t p) { tr_count(t, p, GS_TR_PUBLISHED); }
-  static __device__ __forceinline__ void completed(const Args& t, uint32_t u) { tr_count(t, u, GS_TR_RECEIVED); }
-  static __device__ __forceinline__ void first(const Args&, bool, bool, uint32_t, uint64_t, uint32_t, int) {}
+  static __device__ __forceinline__ void completed(const Args& t, uint32_t u, uint32_t) { tr_count(t, u, GS_TR_RECEIVED); }
+  static __device__ __forceinline__ void first(const Args&, bool, bool, uint32_t, uint64_t, uint32_t, int, uint32_t) {}
 };
 
 // Publishes (publish_new_message, main.rs:101-143): one block per message.
@@ -140,7 +140,7 @@ __device__ __forceinline__ void sends_pub(const RelaxArgs& a, const typename P::
     P::data_arrive(t, w);
     pt.data_acked(t, 1);
   }
-  pt.flush(t, p);
+  pt.flush(t, p, m);
 }
 __global__ __launch_bounds__(TB) void k_traffic_pub(RelaxArgs a, TrafficArgs t) { sends_pub<TrafficAcc>(a, t); }
 
@@ -161,13 +161,13 @@ __device__ __forceinline__ void sends_fwd(const RelaxArgs& a, const typename P::
     const uint32_t m = slot / FP, fl = slot & (FP - 1);
     const uint32_t pm = valid ? a.pub[m] : EMPTY;
     const bool got = key != INF64 && u != pm;
-    P::first(t, got && fl < t.Fe, valid, u, base, LL, lane);
+    P::first(t, got && fl < t.Fe, valid, u, base, LL, lane, m);
     // completed messages (reassembly, main.rs:79-99): every fragment of the group received
     if constexpr (P::completions) {
       constexpr uint64_t gmask = (FP == 64) ? ~0ull : ((1ull << FP) - 1);
       const uint64_t ok = __ballot(valid && (fl >= t.Fe || got));
       const bool lead = fl == 0 && got && !t.collide && ((ok >> (lane & ~(FP - 1))) & gmask) == gmask;
-      if (lead) P::completed(t, u);
+      if (lead) P::completed(t, u, m);
     }
     const uint64_t tt = key >> a.tshift;
     const uint32_t src = (uint32_t)(key & smask);
@@ -215,7 +215,7 @@ __device__ __forceinline__ void sends_fwd(const RelaxArgs& a, const typename P::
       P::data_arrive(t, w);
       pt.data_acked(t, 1);
     }
-    pt.flush(t, u);
+    pt.flush(t, u, m);
   }
 }
 template <int FP>
@@ -262,10 +262,10 @@ __device__ __forceinline__ void sends_gossip(const RelaxArgs& a, const typename 
           wt.data_rx(t);
           pt.data_acked(t, 1);
         }
-        wt.flush(t, w);
+        wt.flush(t, w, m);
       });
     }
-    pt.flush(t, u);
+    pt.flush(t, u, m);
   }
 }
 template <int FP>

@@ -142,6 +142,10 @@ SIGNATURES = {
     "gs_get_peer_given": (i32, [ctypes.c_void_p, P(u64)]),
     "gs_reset_link_deliveries": (i32, [ctypes.c_void_p]),
     "gs_write_link_deliveries": (i32, [ctypes.c_char_p, u32, P(u64), P(u32), P(u64)]),
+    "gs_set_message_costs": (i32, [ctypes.c_void_p, u32]),
+    "gs_message_costs_rows": (i32, [ctypes.c_void_p, P(u64)]),
+    "gs_get_message_costs": (i32, [ctypes.c_void_p, P(u64), u64]),
+    "gs_write_message_costs": (i32, [P(GsConfig), ctypes.c_char_p, P(GsPublish), u64, P(u64)]),
     "gs_set_mesh_events": (i32, [ctypes.c_void_p, u32]),
     "gs_get_mesh_events": (i32, [ctypes.c_void_p, P(u64)]),
     "gs_mesh_series_rows": (i32, [ctypes.c_void_p, P(u32)]),
@@ -363,6 +367,27 @@ def write_link_deliveries(path, row_ptr, col, counts):
                                         _ptr(np.resize(ld.reshape(-1), ld.size + pad), u64))
     if rc:
         raise GossipSimError(rc, "cannot write the link deliveries %s" % path)
+
+
+# gs_get_message_costs columns (GS_MC_*)
+MESSAGE_COST_COLS = ("data_tx", "data_rx", "first", "dup", "ihave_tx", "ihave_rx", "iwant", "delivered")
+
+
+def write_message_costs(cfg, path, schedule, costs):
+    """One TSV line per message: the schedule fields, the MESSAGE_COST_COLS counts and the wire
+    bytes, packets and ACKs they cost (gs_write_message_costs). schedule: a GsPublish array
+    or the (t, publisher, msg_size[, frags]) arrays of the run's messages; costs: uint64
+    [messages, len(MESSAGE_COST_COLS)] (Simulator.message_costs)."""
+    sched = schedule if isinstance(schedule, ctypes.Array) else Simulator._schedule(None, schedule)
+    M = len(sched)
+    mc = np.ascontiguousarray(costs, np.uint64)
+    if mc.ndim != 2 or mc.shape != (M, len(MESSAGE_COST_COLS)):
+        raise GossipSimError(GS_EINVAL, "costs [messages, %d] are needed" % len(MESSAGE_COST_COLS))
+    pad = 1 if M == 0 else 0  # (a pointer to take)
+    rc = lib().gs_write_message_costs(ctypes.byref(cfg.c), str(path).encode(), sched, M,
+                                      _ptr(np.resize(mc.reshape(-1), mc.size + pad), u64))
+    if rc:
+        raise GossipSimError(rc, "cannot write the message costs %s" % path)
 
 
 def write_testnode_metrics(cfg, path, row_ptr, mesh_count, schedule, delay):
@@ -944,6 +969,26 @@ class Simulator:
 
     def write_mesh_series(self, path):
         write_mesh_series(path, self.mesh_series())
+
+    # ---- per-message cost table (gs_set_message_costs) ----
+    def set_message_costs(self, on=True):
+        """Every run / run_log call fills a table with one row per message of its schedule (off by
+        default; one extra pass per batch). Enabling empties the table."""
+        self._check(lib().gs_set_message_costs(self.ctx, 1 if on else 0))
+
+    def message_costs(self):
+        """-> uint64 [messages of the last run / run_log call, len(MESSAGE_COST_COLS)], in schedule
+        order; no rows before a run."""
+        rows = u64(0)
+        self._check(lib().gs_message_costs_rows(self.ctx, ctypes.byref(rows)))
+        mc = np.zeros((rows.value, len(MESSAGE_COST_COLS)), np.uint64)
+        buf = mc if rows.value else np.zeros(1, np.uint64)
+        self._check(lib().gs_get_message_costs(self.ctx, _ptr(buf, u64), rows.value))
+        return mc
+
+    def write_message_costs(self, path, schedule):
+        """The table of the last run / run_log call of `schedule` as TSV, with the wire cost."""
+        write_message_costs(self.cfg, path, schedule, self.message_costs())
 
     # ---- per-peer pubsub event counts (gs_set_pubsub_counts, DESIGN.md §2.14) ----
     def set_pubsub_counts(self, on=True):

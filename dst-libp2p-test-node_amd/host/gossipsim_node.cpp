@@ -28,6 +28,7 @@ void usage() {
           "         [--gml network_topology.gml --yaml shadow.yaml] [--schedule FILE] [--shadowlog PATH] [--metrics PATH]\n"
           "         [--testnode-metrics PATH] [--pubsub-metrics PATH] [--mesh-metrics PATH] [--mesh-series PATH]\n"
           "         [--topology DIALS] [--dump-topology PATH] [--mesh LINKS] [--dump-mesh PATH] [--link-deliveries PATH]\n"
+          "         [--message-costs PATH]\n"
           "  --topology imports a dial list (one \"dialer target\" per line) in place of the random dialing;\n"
           "    --dump-topology writes the dial list of the graph the run used\n"
           "  --mesh imports a mesh (one \"a b\" link per line) in place of the heartbeats' converge (not with\n"
@@ -42,6 +43,8 @@ void usage() {
           "    per-epoch mesh health as CSV, both of the mesh convergence (gs_set_mesh_events)\n"
           "  --link-deliveries writes \"receiver sender publish mesh gossip\" per connection that delivered a fragment\n"
           "    first: who delivered to whom, by the publisher, over the mesh, by IWANT answers (gs_set_link_deliveries)\n"
+          "  --message-costs writes one TSV line per message: copies sent and arrived, first receipts, duplicates,\n"
+          "    IHAVEs, IWANTs, completions and the wire bytes they cost (gs_set_message_costs)\n"
           "env: PEERS CONNECTTO FRAGMENTS MUXER MAXCONNECTIONS GOSSIPSUB_* SELFTRIGGER GS_NODE GS_SEED GS_BATCH\n"
           "     GS_DEVICE\n");
 }
@@ -129,7 +132,7 @@ int main(int argc, char** argv) {
   // after the injector sends it (topogen.py:64-69); tx_time is stamped then
   uint64_t http_us = 3000;
   std::string latencies, gml, yaml, shadowlog, metrics, schedule, testnode, pubsub, mesh_metrics, mesh_series;
-  std::string topology, dump_topology, mesh_file, dump_mesh, link_deliveries;
+  std::string topology, dump_topology, mesh_file, dump_mesh, link_deliveries, message_costs;
   bool set_size = false, set_msgs = false, set_delay = false, set_t0 = false, device_log = false;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -166,6 +169,7 @@ int main(int argc, char** argv) {
     else if (a == "--mesh") mesh_file = next();  // a link list ("a b" per line) in place of the converge
     else if (a == "--dump-mesh") dump_mesh = next();  // the links of the mesh the run used
     else if (a == "--link-deliveries") link_deliveries = next();  // per-link first deliveries (P2, main.rs:252-258)
+    else if (a == "--message-costs") message_costs = next();  // what each message cost
     else if (a == "--schedule") schedule = next();  // rows: t_pub_ns publisher msg_size [frags]
     else { usage(); return 2; }
   }
@@ -216,6 +220,7 @@ int main(int argc, char** argv) {
   if (!pubsub.empty() && (st = gs_set_pubsub_counts(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_pubsub_counts");
   if (!link_deliveries.empty() && (st = gs_set_link_deliveries(ctx, 1)) != GS_OK)
     return die(ctx, st, "gs_set_link_deliveries");
+  if (!message_costs.empty() && (st = gs_set_message_costs(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_message_costs");
   const bool mesh_events = !mesh_metrics.empty() || !mesh_series.empty();
   if (mesh_events && (st = gs_set_mesh_events(ctx, 1)) != GS_OK) return die(ctx, st, "gs_set_mesh_events");
   if (topology.empty()) {
@@ -401,6 +406,15 @@ int main(int argc, char** argv) {
     if ((st = gs_get_link_deliveries(ctx, ld.data())) != GS_OK) return die(ctx, st, "gs_get_link_deliveries");
     if ((st = gs_write_link_deliveries(link_deliveries.c_str(), cfg.peers, row.data(), col.data(), ld.data())) != GS_OK)
       return die(ctx, st, "gs_write_link_deliveries");
+  }
+  if (!message_costs.empty()) {  // (the table is the last gs_run / gs_run_log call's: the whole schedule)
+    uint64_t rows = 0;
+    if ((st = gs_message_costs_rows(ctx, &rows)) != GS_OK) return die(ctx, st, "gs_message_costs_rows");
+    std::vector<uint64_t> mc((size_t)rows * GS_MC_COLS + 1);
+    if ((st = gs_get_message_costs(ctx, mc.data(), rows)) != GS_OK) return die(ctx, st, "gs_get_message_costs");
+    if (rows != sched.size()) return die(ctx, GS_ESTATE, "gs_message_costs_rows");
+    if ((st = gs_write_message_costs(&cfg, message_costs.c_str(), sched.data(), rows, mc.data())) != GS_OK)
+      return die(ctx, st, "gs_write_message_costs");
   }
   gs_destroy(ctx);
   return 0;

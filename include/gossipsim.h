@@ -610,6 +610,46 @@ gs_status gs_reset_link_deliveries(struct gs_ctx* ctx);
 gs_status gs_write_link_deliveries(const char* path, uint32_t peers, const uint64_t* row_ptr, const uint32_t* col,
                                    const uint64_t* counts);
 
+/* ---- per-message cost table --------------------------------
+ * What each message of one gs_run / gs_run_log call cost: the sends, arrivals
+ * and losses the per-peer traffic and pubsub counts enumerate, reduced by
+ * message instead of by peer. A schedule that sweeps message size or chunk count
+ * (gs_publish.frags) gets every message's cost from one call. */
+enum { GS_MC_DATA_TX = 0,   /* fragment copies sent: the publisher's sends, forwards and IWANT    */
+                            /* answers; duplicates and lost copies included                       */
+       GS_MC_DATA_RX = 1,   /* copies that arrived                                                */
+       GS_MC_FIRST = 2,     /* first receipts of a fragment at a non-publisher                    */
+       GS_MC_DUP = 3,       /* duplicates: DATA_RX - FIRST                                        */
+       GS_MC_IHAVE_TX = 4, GS_MC_IHAVE_RX = 5,  /* IHAVE RPCs sent / arrived                      */
+       GS_MC_IWANT = 6,     /* IWANT RPCs (always delivered: sent equals arrived)                 */
+       GS_MC_DELIVERED = 7, /* completions at non-publishers (every fragment received)            */
+       GS_MC_COLS = 8 };
+/* 1: every gs_run and gs_run_log call fills a table on the device with one row
+ * per message of its schedule, in schedule order (whatever batches the run cuts
+ * or regroups). The table belongs to the most recent call: it is zeroed at the
+ * call's start, does not accumulate, and gs_reset_stats leaves it alone. One
+ * extra pass over each batch's final keys (off by default, diagnostic). Enabling
+ * (again) empties the table. Partitioned mode (gs_part_begin,
+ * gs_run_partitioned*) returns GS_EUNSUPPORTED while the switch is on.
+ * gs_save_state does not carry the table: a loaded context has the switch off. */
+gs_status gs_set_message_costs(struct gs_ctx* ctx, uint32_t enable);
+/* The table's rows: the messages of the last call; 0 before any run and after
+ * the switch is enabled. GS_ESTATE while the switch is off. */
+gs_status gs_message_costs_rows(struct gs_ctx* ctx, uint64_t* rows);
+/* out[rows][GS_MC_COLS]. GS_ESTATE while the switch is off; GS_EINVAL when rows
+ * is not gs_message_costs_rows' count. */
+gs_status gs_get_message_costs(struct gs_ctx* ctx, uint64_t* out, uint64_t rows);
+/* Host only. One TSV line per message under a '#' header line: its index, the
+ * schedule fields (t_pub_ns, publisher, msg_size, chunks), the GS_MC_COLS counts,
+ * and the wire cost derived from them with gs_wire_bytes, gs_wire_packets and
+ * gs_control_packets: tx and rx bytes and packets (fragment copies, IHAVEs and
+ * IWANTs), the pure ACK packets (ceil(packets / 2) per arrival) and their bytes.
+ * costs[n_msgs][GS_MC_COLS] is a host copy (gs_get_message_costs). GS_EINVAL: a
+ * null argument, a message no node can publish (its fragment too short), a path
+ * that cannot be written. */
+gs_status gs_write_message_costs(const gs_config* cfg, const char* path, const gs_publish* sched, uint64_t n_msgs,
+                                 const uint64_t* costs);
+
 /* ---- mesh events and per-epoch mesh health -----------------
  * What go-test-node/metrics.go:164-190 counts per node (GRAFT and PRUNE RPCs
  * sent and received) and what its tracer follows (metrics.go:224-258 mesh size,
@@ -848,7 +888,8 @@ gs_status gs_comm_destroy(gs_comm* comm);
  * peers' rows; gs_stats.ms_batches counts them). Collective over the
  * communicator. Results are bit-identical to gs_run. GS_EUNSUPPORTED: per-peer
  * traffic (gs_set_traffic), per-peer pubsub counts (gs_set_pubsub_counts),
- * per-link first deliveries (gs_set_link_deliveries), and sink summaries of a
+ * per-link first deliveries (gs_set_link_deliveries), per-message costs
+ * (gs_set_message_costs), and sink summaries of a
  * message-sharded batch.
  * Every sinks[i] follows gs_result_sink's rules (GS_EINVAL otherwise); on_lat
  * receives [n][own peers] u16, and the parts' blocks side by side are gs_run's

@@ -20,6 +20,7 @@ pub const GS_TRAFFIC_COLS: usize = 12; // GS_TR_*: tx/rx bytes, packets, header 
 pub const GS_MESH_EVENT_COLS: usize = 7; // GS_ME_*: graft tx/rx, prune tx/rx, mesh add/del/drop
 pub const GS_MESH_SERIES_COLS: usize = 12; // GS_MS_*: online, no_peers, low, healthy, over, links, then the six event sums
 pub const GS_PUBSUB_COLS: usize = 8; // GS_PS_*: msg tx/rx, first, dup, ihave tx/rx, iwant tx/rx
+pub const GS_MC_COLS: usize = 8; // GS_MC_*: data tx/rx, first, dup, ihave tx/rx, iwant, delivered
 pub const GS_LD_COLS: usize = 3; // GS_LD_*: first deliveries by the publisher, over the mesh, by IWANT answers
 pub const GS_HIST_BINS: usize = 64;
 pub const GS_DELAY_BUCKETS: usize = 12; // le = 1 .. 10000 ms (nim gossipsub-queues main.nim:59)
@@ -168,6 +169,11 @@ extern "C" {
     pub fn gs_reset_link_deliveries(ctx: *mut gs_ctx) -> gs_status;
     pub fn gs_write_link_deliveries(path: *const c_char, peers: u32, row_ptr: *const u64, col: *const u32,
                                     counts: *const u64) -> gs_status;
+    pub fn gs_set_message_costs(ctx: *mut gs_ctx, enable: u32) -> gs_status;
+    pub fn gs_message_costs_rows(ctx: *mut gs_ctx, rows: *mut u64) -> gs_status;
+    pub fn gs_get_message_costs(ctx: *mut gs_ctx, out: *mut u64, rows: u64) -> gs_status;
+    pub fn gs_write_message_costs(cfg: *const gs_config, path: *const c_char, sched: *const gs_publish, n_msgs: u64,
+                                  costs: *const u64) -> gs_status;
     pub fn gs_set_mesh_events(ctx: *mut gs_ctx, enable: u32) -> gs_status;
     pub fn gs_get_mesh_events(ctx: *mut gs_ctx, out: *mut u64) -> gs_status;
     pub fn gs_mesh_series_rows(ctx: *mut gs_ctx, rows: *mut u32) -> gs_status;
