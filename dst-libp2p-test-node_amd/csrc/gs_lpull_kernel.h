@@ -67,7 +67,11 @@
 
 constexpr uint32_t LP_KMAX = 12;  // ring of destination-window lists
 constexpr uint32_t LP_SW = 16;    // u32 words of per-row state: list lengths [0..11] (slot = window % K), log length
-constexpr uint32_t LP_LOG = 15;   // state word holding the final-log length
+// State word holding the row's final lanes. Rows of single-fragment lanes (FP = 1): every form
+// counts them, the publisher's own lanes included (k_lpub), and where a final log is kept the
+// count is its length; step 0 takes a row whose count is the batch's lanes per row out of the
+// pass (k_lpull's DONE). Fragment groups: the final-log length only.
+constexpr uint32_t LP_LOG = 15;
 // state word set (k_lpubnb) on every batch publisher and its mesh (churn: CSR)
 // neighbours: only those rows' emit step needs the publishers (LPullArgs::pubw)
 constexpr uint32_t LP_PUB = 12;
@@ -506,6 +510,15 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
   // mesh of a lane's epoch is a mask over it)
   constexpr uint32_t HW = CHN ? CELL_W : MESH_W;
   constexpr uint32_t LMAX = CH * 64;
+  // Finished rows: rows of single-fragment lanes on the frozen mesh
+  // keep the count of their final lanes in state word LP_LOG, and step 0 books a row whose
+  // count is the batch's lanes per row (L = B * FP = B) without visiting it. Not fragment
+  // groups (a group's lanes are final one by one and the word is the log length there) and
+  // not churn (a row's mesh changes under its lanes, and a lane offline in its epochs is never final).
+  // <1, 8, IDW, .., GOS> stays as it was: it runs with scratch at 80 VGPRs and the test's
+  // one more value in the 64-row scan cost it another 4 B per lane (its gossip windows
+  // have their row-done bits; nothing reads its rows' word).
+  constexpr bool DONE = FP == 1 && !CHN && !(IDW && GOS && CH == 8);
   __shared__ LPullLds<CH> Ls;
   uint64_t* me = a.ctrl + (a.pass % 3) * 4;
   uint64_t lo, mode;
@@ -659,7 +672,10 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
   // 0. lane l: row base + l * stride is active if a neighbour sent records
   //    (PULL), entries are due in window c, or it may take IHAVEs (a gossip
   //    window, a lane not final); an inactive row is only booked: no records
-  //    from it next pass, its pending windows into nmh
+  //    from it next pass, its pending windows into nmh. A finished row (DONE: its
+  //    count of final lanes is the batch's) is inactive whatever its neighbours
+  //    sent, without the gather of their counts, and books no pending window:
+  //    every lane its list entries name is final, so they drive no pass
   uint64_t am;
   {
     const uint32_t wl = base + (uint32_t)lane * stride;
@@ -672,6 +688,9 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
         const uint4 v = sp[k];
         s4[k * 4] = v.x; s4[k * 4 + 1] = v.y; s4[k * 4 + 2] = v.z; s4[k * 4 + 3] = v.w;
       }
+      // the row's final lanes, from the 64-byte line of the lengths; every lane final: L = B of them
+      [[maybe_unused]] bool done = false;
+      if constexpr (DONE) done = a.st[(size_t)wl * LP_SW + LP_LOG] == LL;
       // the nearest pending window; cs and kk pass through an empty asm so that
       // the per-slot offsets and tests are computed here, not hoisted out of the
       // row loop (24 more scalars live across every row: SGPR spills)
@@ -685,9 +704,10 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
         mo = umin32(mo, j >= cs ? j - cs : j + kk - cs);
       }
       // (window c + k starts at sat32(hlo64 + k * dG) = sat32(hlo + k * dG): once hlo64 is past 32 bits both are ~0)
-      const uint32_t mh = mo == ~0u ? ~0u : sat32((uint64_t)hlo + (uint64_t)mo * hspan);
+      const uint32_t mh = mo == ~0u || done ? ~0u : sat32((uint64_t)hlo + (uint64_t)mo * hspan);
       if (GOS && gw) act |= !((a.rowdone[wl >> 5] >> (wl & 31)) & 1u) && (!CHN || a.gtag[wl] == gbk);
-      if (pk_f(p0, PK_PULL, 1) && !act) {
+      act &= !done;
+      if (pk_f(p0, PK_PULL, 1) && !act && !done) {
         // the counts' base as a value of this block: each of the gathers below sits under
         // its own lane mask, and the long-lived pointer was read back from its spill lane
         // in front of every one of them
@@ -1395,7 +1415,10 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
       const uint32_t ps = pk_get(), K = pk_f(ps, PK_K, 4), cslot = pk_f(ps, PK_CS, 4);
       uint32_t nv = sv;  // lane j < K: slot j (window c + lwin), emptied if it is window c's
       if (lane < (int)K) nv = lane == (int)cslot ? 0u : sv + addl;
-      if (!NOLOG && lane == (int)LP_LOG) nv = logc;
+      // the final lanes: where a log is kept its length, else (no-log twin, IDONTWANT's dense
+      // keys) the lane's own word plus this visit's finals (cnt is wave-uniform)
+      if constexpr (DONE && (NOLOG || IDW)) nv += lane == (int)LP_LOG ? cnt : 0u;
+      else if (!NOLOG && lane == (int)LP_LOG) nv = logc;
       if (lane <= (int)LP_LOG) a.st[(size_t)w * LP_SW + lane] = nv;
       if (lane < (int)K && nv) nmh = umin32(nmh, lwhi);
     }
@@ -1864,12 +1887,13 @@ __global__ void k_lpub(LPullArgs a, uint32_t Fe) {
   const uint32_t p = a.pub[m] - a.u0;   // local row
   const uint32_t j = i & 63, q = i >> 6;  // transposed: lane j's u16, bit q
   atomicOr(&a.fin[(size_t)p * LP_FW + (j >> 1)], 1u << (16 * (j & 1) + q));
+  // one more final lane of the row (LP_LOG), where a log is kept the entry's position
+  const uint32_t pos = atomicAdd(&a.st[(size_t)p * LP_SW + LP_LOG], 1u);
   if (a.idw) {  // dense keys (IDONTWANT batches)
     a.keys[(size_t)p * a.L + i] = (uint64_t)(p + a.u0);
     return;
   }
   if (!a.keys) return;  // no-log batch (the publisher's own key is no delivery)
-  const uint32_t pos = atomicAdd(&a.st[(size_t)p * LP_SW + LP_LOG], 1u);
   a.keys[(size_t)p * a.L + pos] = (uint64_t)(p + a.u0);
   a.flane[(size_t)p * a.L + pos] = (uint16_t)i;
 }

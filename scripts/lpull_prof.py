@@ -12,7 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dst-libp2p-test-node_amd"))
 import gossipsim  # noqa: E402
 
-gossipsim.LIB_PATH = os.path.join(ROOT, "prof_build", "libgossipsim.so")
+# (GOSSIPSIM_LIB: another -DGS_PULL_PROF build, e.g. scripts/build_variant.sh's of a parent commit)
+gossipsim.LIB_PATH = os.environ.get("GOSSIPSIM_LIB") or os.path.join(ROOT, "prof_build", "libgossipsim.so")
 peers = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 L = gossipsim.lib()
 L.gs_debug_pull_prof.argtypes = [ctypes.c_void_p]
