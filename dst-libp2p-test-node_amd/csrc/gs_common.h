@@ -1,6 +1,7 @@
 // gs_common.h — spec-level constants and pure functions shared by the host
 // code and the gfx950 kernels of libgossipsim. Nothing here
-// touches the device; kernels include it for the inline helpers.
+// touches device memory; kernels include it for the inline helpers (the
+// wave reductions at the end are device code, compiled by hipcc only).
 #pragma once
 #include <stdint.h>
 
@@ -114,5 +115,35 @@ GS_HD bool frag_collide(uint32_t node, uint64_t msg_size, uint32_t F) {
 
 // Serialisation time in ns of `bytes` at `bps` (ceil).
 GS_HD uint64_t ser_ns(uint64_t bytes, uint64_t bps) { return (bytes * 8000000000ull + bps - 1) / bps; }
+
+#if defined(__HIPCC__)
+// Wave-wide reductions of a 32-bit value in registers: an inclusive
+// scan inside each row of 16 lanes by DPP row shifts (1, 2, 4, 8), then the two row
+// broadcasts of gfx9 / CDNA (lane 15 of a row into the next row, rows 1 and 3; lane 31
+// into rows 2 and 3), so that lane 63 holds the wave's result. No LDS crossbar
+// (ds_bpermute), no lane-select arithmetic and no lgkmcnt wait, unlike a __shfl_xor
+// butterfly. A lane that a control leaves out (the first lanes of a row shift, the rows
+// outside a broadcast's row mask) reads 0, so op(x, 0) must be x. Every lane of the
+// wave must be active at the call.
+template <class Op>
+__device__ __forceinline__ uint32_t wave_reduce32(uint32_t v, Op op) {
+#define GS_DPP(ctrl, rows) (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rows, 0xf, false)
+  v = op(v, GS_DPP(0x111, 0xf));  // row_shr:1
+  v = op(v, GS_DPP(0x112, 0xf));  // row_shr:2
+  v = op(v, GS_DPP(0x114, 0xf));  // row_shr:4
+  v = op(v, GS_DPP(0x118, 0xf));  // row_shr:8
+  v = op(v, GS_DPP(0x142, 0xa));  // row_bcast:15
+  v = op(v, GS_DPP(0x143, 0xc));  // row_bcast:31
+#undef GS_DPP
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+__device__ __forceinline__ uint32_t wave_or32(uint32_t v) {
+  return wave_reduce32(v, [](uint32_t x, uint32_t y) { return x | y; });
+}
+// (the sum must fit 32 bits)
+__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
+  return wave_reduce32(v, [](uint32_t x, uint32_t y) { return x + y; });
+}
+#endif
 
 }  // namespace gs

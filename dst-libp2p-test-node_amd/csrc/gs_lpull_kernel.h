@@ -519,6 +519,13 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
   // one more value in the 64-row scan cost it another 4 B per lane (its gossip windows
   // have their row-done bits; nothing reads its rows' word).
   constexpr bool DONE = FP == 1 && !CHN && !(IDW && GOS && CH == 8);
+  // The wave-wide reductions of a visit (the touched-chunk mask, the gossip forms' count of
+  // final lanes, churn's receiver mask) by DPP row operations in registers (wave_or32,
+  // gs_common.h) instead of six __shfl_xor steps, each an LDS
+  // round trip (ds_bpermute) with its lane-select arithmetic and its lgkmcnt(0). Rows of
+  // single-fragment lanes, except the gossip forms of 512 lanes: those three run with scratch
+  // and the DPP form cost each another 4 B per lane; fragment groups sit at their VGPR limit.
+  constexpr bool DPPR = FP == 1 && !(GOS && CH == 8);
   __shared__ LPullLds<CH> Ls;
   uint64_t* me = a.ctrl + (a.pass % 3) * 4;
   uint64_t lo, mode;
@@ -1198,8 +1205,13 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
     } else if constexpr (GOS) {
       if (gossip_row) glp_ihave(a, CW, w, sw, finT, wlo, gR, lat, supr, supr + Sr, cb, niw, err);
     }
-    for (int off = 32; off > 0; off >>= 1) cb |= __shfl_xor(cb, off);
-    cb = __builtin_amdgcn_readfirstlane(cb);
+    // the chunks any lane touched, as a scalar
+    if constexpr (DPPR) {
+      cb = wave_or32(cb);
+    } else {
+      for (int off = 32; off > 0; off >>= 1) cb |= __shfl_xor(cb, off);
+      cb = __builtin_amdgcn_readfirstlane(cb);
+    }
     wave_lds_sync();
     // next row's lists
     if constexpr (EARLY) {
@@ -1408,7 +1420,12 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
     if (nfin) reinterpret_cast<uint16_t*>(a.fin + (size_t)w * LP_FW)[lane] = (uint16_t)finT;
     if constexpr (GOS) {  // every lane final: no IHAVE can matter to this row any more
       // (the lanes that can be final: F per message, one under defect D8; padding lanes never are)
-      if (nfin && wave_sum((uint64_t)__popc(finT & 0xFFFFu)) == a.B * (a.collide ? 1u : a.F) && lane == 0)
+      // (at most PULL_LMAX final lanes: the sum fits 32 bits)
+      const auto nfl = [&]() -> uint64_t {
+        if constexpr (DPPR) return wave_sum32((uint32_t)__popc(finT & 0xFFFFu));
+        else return wave_sum((uint64_t)__popc(finT & 0xFFFFu));
+      };
+      if (nfin && nfl() == a.B * (a.collide ? 1u : a.F) && lane == 0)
         atomicOr(&a.rowdone[w >> 5], 1u << (w & 31));
     }
     {
@@ -1423,7 +1440,9 @@ __global__ __launch_bounds__(TB, (CH <= 8 ? 6 : 4)) void k_lpull(LPullArgs a) {
       if (lane < (int)K && nv) nmh = umin32(nmh, lwhi);
     }
     if constexpr (CHN) {
-      for (int off = 32; off > 0; off >>= 1) uni |= __shfl_xor(uni, off);
+      if constexpr (DPPR) uni = (uint64_t)wave_or32((uint32_t)(uni >> 32)) << 32 | wave_or32((uint32_t)uni);
+      else
+        for (int off = 32; off > 0; off >>= 1) uni |= __shfl_xor(uni, off);
       if (lane == 0) wuni[w] = uni;
     }
     if (lane == 0) wcnt_of(pk_get())[w] = ecnt;
