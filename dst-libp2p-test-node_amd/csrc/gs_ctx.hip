@@ -276,6 +276,43 @@ extern "C" gs_status gs_set_mesh_links(gs_ctx* ctx, uint64_t n_links, const uint
   GS_API_END(ctx)
 }
 
+// ---- a caller's outages in place of the churn draw (gs_outages.h) ----
+static void outages_state(gs_ctx* ctx) {
+  if (!ctx->cfg.churn_ppm)
+    ctx->fail(GS_ESTATE, "outages on a context without churn (churn_ppm != 0 makes a churn context; its value "
+                         "is not read while a schedule is imported)");
+  if (ctx->part_open) ctx->fail(GS_ESTATE, "a partitioned batch is in flight (gs_part_finish first)");
+}
+
+extern "C" gs_status gs_set_outages(gs_ctx* ctx, uint64_t n, const uint32_t* peer, const uint32_t* h_from,
+                                    const uint32_t* h_to) {
+  GS_API_BEGIN(ctx)
+  if (n && (!peer || !h_from || !h_to)) ctx->fail(GS_EINVAL, "null outage arrays");
+  outages_state(ctx);
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  import_outages(*ctx, n, peer, h_from, h_to);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_clear_outages(gs_ctx* ctx) {
+  GS_API_BEGIN(ctx)
+  if (!ctx->outages_on) return GS_OK;
+  outages_state(ctx);
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  clear_outages(*ctx);
+  GS_API_END(ctx)
+}
+
+extern "C" gs_status gs_get_offline(gs_ctx* ctx, uint32_t h_lo, uint32_t h_hi, uint64_t* bits) {
+  GS_API_BEGIN(ctx)
+  if (!bits) ctx->fail(GS_EINVAL, "null bits");
+  if (!ctx->cfg.churn_ppm) ctx->fail(GS_ESTATE, "gs_get_offline on a context without churn (churn_ppm = 0)");
+  if (h_hi < h_lo) ctx->fail(GS_EINVAL, "gs_get_offline: h_hi < h_lo");
+  GS_HIP(hipSetDevice(ctx->cfg.device));
+  get_offline(*ctx, h_lo, h_hi, bits);
+  GS_API_END(ctx)
+}
+
 extern "C" gs_status gs_get_mesh(gs_ctx* ctx, uint32_t* mesh, uint8_t* count) {
   GS_API_BEGIN(ctx)
   if (!ctx->mesh_built) ctx->fail(GS_ESTATE, "gs_mesh_converge first");
@@ -669,6 +706,9 @@ extern "C" gs_status gs_save_state(gs_ctx* ctx, const char* path) {
   if (!path) ctx->fail(GS_EINVAL, "null path");
   if (!ctx->links_set || !ctx->topo_built) ctx->fail(GS_ESTATE, "gs_set_links and gs_build_topology first");
   if (ctx->part_open) ctx->fail(GS_ESTATE, "a partitioned batch is in flight");
+  if (ctx->outages_on)
+    ctx->fail(GS_EUNSUPPORTED, "gs_save_state with imported outages: the file does not carry the schedule, and a "
+                               "loaded context would replay the draw (gs_clear_outages first)");
   GS_HIP(hipSetDevice(ctx->cfg.device));
   StateFile sf;
   if (!(sf.f = fopen(path, "wb"))) ctx->fail(GS_EINVAL, std::string("cannot open ") + path);

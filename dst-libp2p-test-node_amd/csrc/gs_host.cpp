@@ -651,6 +651,93 @@ extern "C" gs_status gs_read_dials(const char* path, uint32_t* dialer, uint32_t*
   return rows > cap ? GS_ERANGE : GS_OK;
 }
 
+// An outage file: "peer t_down_ns [t_up_ns]" per line (a missing third column: the peer never
+// returns, t_up = UINT64_MAX), comments, blank lines and the cap contract as gs_read_dials. A
+// line that is none of these is GS_EINVAL with *n = the line's number (from 1).
+extern "C" gs_status gs_read_outages(const char* path, uint32_t* peer, uint64_t* t_down_ns, uint64_t* t_up_ns,
+                                     uint64_t cap, uint64_t* n) {
+  if (!path || !n) return GS_EINVAL;
+  *n = 0;
+  FILE* f = fopen(path, "r");
+  if (!f) return GS_EINVAL;
+  char* line = nullptr;
+  size_t line_cap = 0;
+  uint64_t rows = 0, lineno = 0;
+  gs_status st = GS_OK;
+  while (getline(&line, &line_cap, f) != -1) {
+    lineno++;
+    char* h = strchr(line, '#');
+    if (h) *h = 0;
+    char* q = line;
+    while (*q && isspace((unsigned char)*q)) q++;
+    if (!*q) continue;  // blank / comment
+    unsigned long long v[3] = {0, 0, ~0ull};
+    int k = 0;
+    bool ok = true;
+    for (; k < 3 && ok; k++) {
+      while (*q && isspace((unsigned char)*q)) q++;
+      if (!*q && k == 2) break;              // two columns
+      ok = isdigit((unsigned char)*q) != 0;  // (strtoull alone would take a sign)
+      if (!ok) break;
+      char* end = nullptr;
+      errno = 0;
+      v[k] = strtoull(q, &end, 10);
+      ok = end != q && errno == 0 && (k > 0 || v[k] <= 0xFFFFFFFFull) && (!*end || isspace((unsigned char)*end));
+      q = end;
+    }
+    while (ok && *q && isspace((unsigned char)*q)) q++;
+    if (!ok || *q || k < 2) { st = GS_EINVAL; break; }  // not a number, one column, or more than three
+    if (peer && t_down_ns && t_up_ns && rows < cap) {
+      peer[rows] = (uint32_t)v[0];
+      t_down_ns[rows] = v[1];
+      t_up_ns[rows] = v[2];
+    }
+    rows++;
+  }
+  free(line);
+  fclose(f);
+  if (st != GS_OK) {
+    *n = lineno;
+    return st;
+  }
+  *n = rows;
+  return rows > cap ? GS_ERANGE : GS_OK;
+}
+
+// The times of a trace as heartbeat epochs (DESIGN.md §2.8 "A caller's outages"): a peer is
+// offline in epoch h >= 1 iff it is down at the heartbeat that starts the epoch,
+// t_down <= hb_phase + h * heartbeat < t_up.
+extern "C" gs_status gs_outage_epochs(const gs_config* cfg, uint64_t n, const uint32_t* peer, const uint64_t* t_down_ns,
+                                      const uint64_t* t_up_ns, uint32_t* peer_out, uint32_t* h_from, uint32_t* h_to,
+                                      uint64_t* n_out) {
+  if (!cfg || !n_out || cfg->heartbeat_ns == 0) return GS_EINVAL;
+  *n_out = 0;
+  if (n && (!peer || !t_down_ns || !t_up_ns || !peer_out || !h_from || !h_to)) return GS_EINVAL;
+  const uint64_t hb = cfg->heartbeat_ns, ph = cfg->hb_phase_ns;
+  auto first_hb_at_or_after = [&](uint64_t t) -> uint64_t {  // ceil((t - phase) / heartbeat), 0 at or before the phase
+    if (t <= ph) return 0;
+    const uint64_t d = t - ph;
+    return d / hb + (d % hb ? 1 : 0);
+  };
+  uint64_t k = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    if (t_up_ns[i] < t_down_ns[i]) return GS_EINVAL;
+    uint64_t a = first_hb_at_or_after(t_down_ns[i]);
+    if (a < 1) a = 1;
+    const bool forever = t_up_ns[i] == UINT64_MAX;
+    const uint64_t b = forever ? GS_OUTAGE_FOREVER : first_hb_at_or_after(t_up_ns[i]);
+    if (a >= GS_OUTAGE_FOREVER || (!forever && b >= GS_OUTAGE_FOREVER)) return GS_ERANGE;  // an epoch past 2^32 - 2
+    if (a >= b) continue;  // no heartbeat inside the outage
+    const uint32_t u = peer[i];  // (the outputs may be the inputs' arrays: k <= i)
+    peer_out[k] = u;
+    h_from[k] = (uint32_t)a;
+    h_to[k] = (uint32_t)b;
+    k++;
+  }
+  *n_out = k;
+  return GS_OK;
+}
+
 // One "dialer target" line per F_OUT entry of the CSR, in row order.
 extern "C" gs_status gs_write_dials(const char* path, uint32_t peers, const uint64_t* row_ptr, const uint32_t* col,
                                     const uint8_t* flags) {

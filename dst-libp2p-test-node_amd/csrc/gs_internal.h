@@ -232,6 +232,29 @@ struct Ctx {
   DevBuf<uint8_t> d_mcnt;    // [N]
   DevBuf<uint8_t> d_pst;     // event-driven churn epochs: [PS_PLANES][N] per-peer flags and counts
   DevBuf<uint64_t> d_offlin; // offline bitsets of a run of churn epochs, [epochs + 1][(N+63)/64]
+  // a caller's outages in place of the draw (gs_set_outages, gs_outages.h): each peer's sorted, disjoint
+  // intervals as a CSR of h_to << 32 | h_from words, on the device and on the host
+  bool outages_on = false;
+  uint64_t outage_fp = 0;       // fingerprint of the imported schedule; 0: the draw
+  DevBuf<uint32_t> d_og_ptr;    // [N+1]
+  DevBuf<uint64_t> d_og_iv;
+  std::vector<uint32_t> og_ptr;
+  std::vector<uint64_t> og_iv;
+  // Is peer u offline in heartbeat epoch h, from whichever source is active (the host's
+  // publisher-online checks; the device's bitsets come from k_offline_range / k_outage_range).
+  bool offline(uint32_t u, uint64_t h) const {
+    if (!outages_on) return offline_draw(cfg.seed, cfg.churn_ppm, cfg.churn_down, u, h);
+    if (h == 0) return false;
+    uint32_t lo = og_ptr[u], hi = og_ptr[u + 1];
+    const uint32_t b = lo;
+    while (lo < hi) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if ((uint32_t)og_iv[mid] <= h) lo = mid + 1; else hi = mid;
+    }
+    if (lo == b) return false;
+    const uint32_t to = (uint32_t)(og_iv[lo - 1] >> 32);
+    return to == 0xFFFFFFFFu || h < to;
+  }
 
   // dissemination (per batch)
   DevBuf<uint64_t> d_keys;   // [N * B * FP] peer-major (u, m, f)
@@ -474,6 +497,10 @@ void graph_replaced(Ctx& c);  // the context holds another graph than before (an
 uint32_t run_mesh(Ctx& c, uint32_t max_heartbeats);
 void import_mesh_ell(Ctx& c, const uint32_t* mesh, const uint8_t* count);                  // gs_set_mesh
 void import_mesh_links(Ctx& c, uint64_t n, const uint32_t* a, const uint32_t* b);         // gs_set_mesh_links
+// a caller's outages in place of the churn draw (gs_outages.h)
+void import_outages(Ctx& c, uint64_t n, const uint32_t* peer, const uint32_t* h_from, const uint32_t* h_to);  // gs_set_outages
+void clear_outages(Ctx& c);                                                                                  // gs_clear_outages
+void get_offline(Ctx& c, uint64_t h_lo, uint64_t h_hi, uint64_t* bits);                                        // gs_get_offline
 inline void ensure_cus(Ctx& c) {
   if (c.num_cus == 0) {
     hipDeviceProp_t prop;

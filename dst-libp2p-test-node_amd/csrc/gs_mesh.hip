@@ -821,6 +821,10 @@ __global__ __launch_bounds__(TB) void k_offline_range(uint32_t N, uint64_t seed,
   }
 }
 
+}  // namespace
+#include "gs_outages.h"  // k_outage_range, the twin over a caller's outages; offline_range launches one of the two
+namespace {
+
 // Start of a run of epochs: mesh counts, and the departures of its first
 // epoch. Grid-stride, one row per group of G lanes (group-uniform loop).
 template <int G>
@@ -1200,12 +1204,7 @@ void ev_epochs(Ctx& c, MeshArgs a, uint64_t h0, uint64_t h1, bool ring, bool cou
   // their slots (offline bits and targets are written in parallel over epochs)
   const uint64_t hr = ring && E > c.ring_R ? h1 + 1 - c.ring_R : h0;
   c.d_offlin.alloc((size_t)(E + 1) * w64);
-  for (uint64_t y0 = 0; y0 < E + 1; y0 += 32768) {  // grid.y limit
-    const uint32_t ny = (uint32_t)std::min<uint64_t>(32768, E + 1 - y0);
-    k_offline_range<<<dim3(blocks(N), ny), TB, 0, s>>>(N, c.cfg.seed, c.cfg.churn_ppm, c.cfg.churn_down,
-                                                       h0 - 1 + y0, c.d_offlin.p + y0 * w64, w64,
-                                                       ring ? c.d_ring_off.p : nullptr, c.ring_R, hr);
-  }
+  offline_range(c, s, h0 - 1, E + 1, c.d_offlin.p, w64, ring ? c.d_ring_off.p : nullptr, hr);
   c.d_pst.alloc((size_t)PS_PLANES * N);
   GS_HIP(hipMemsetAsync(c.d_pst.p, 0, (size_t)PS_MC * N, s));         // flags clear
   GS_HIP(hipMemsetAsync(c.d_pst.p + (size_t)PS_DIRTY * N, 1, N, s));  // first epoch: extract every row
@@ -1428,12 +1427,7 @@ EvRun* chain_begin(Ctx& c, uint64_t h1, hipStream_t s, std::function<void(uint64
   r->hook = std::move(hook);
   const uint64_t E = h1 - r->h0 + 1;
   c.d_offlin.alloc((size_t)(E + 1) * r->w64);
-  for (uint64_t y0 = 0; y0 < E + 1; y0 += 32768) {  // grid.y limit
-    const uint32_t ny = (uint32_t)std::min<uint64_t>(32768, E + 1 - y0);
-    k_offline_range<<<dim3(blocks(N), ny), TB, 0, s>>>(N, c.cfg.seed, c.cfg.churn_ppm, c.cfg.churn_down,
-                                                       r->h0 - 1 + y0, c.d_offlin.p + y0 * r->w64, r->w64,
-                                                       c.d_ring_off.p, c.ring_R, r->h0);
-  }
+  offline_range(c, s, r->h0 - 1, E + 1, c.d_offlin.p, r->w64, c.d_ring_off.p, r->h0);
   c.d_pst.alloc((size_t)PS_PLANES * N);
   GS_HIP(hipMemsetAsync(c.d_pst.p, 0, (size_t)PS_MC * N, s));
   GS_HIP(hipMemsetAsync(c.d_pst.p + (size_t)PS_DIRTY * N, 1, N, s));

@@ -203,6 +203,7 @@ struct PRun {
     }
     if (c.topo_fp) h = (h ^ c.topo_fp) * 1099511628211ull;  // an imported graph's fingerprint (0: the built one)
     if (c.mesh_fp) h = (h ^ c.mesh_fp) * 1099511628211ull;  // an imported mesh's (0: a converged one)
+    if (c.outage_fp) h = (h ^ c.outage_fp) * 1099511628211ull;  // an imported outage schedule's (0: the draw)
     const uint64_t sig[8] = {c.cfg.peers, c.cfg.batch, c.cfg.lazy_gossip, c.cfg.idontwant,
                              c.cfg.churn_ppm, c.cfg.fragments, c.cfg.seed, h ^ n_msgs};
     static_assert(2 * sizeof sig <= HP_SCRATCH * 8, "the MIN and MAX rows in the mirror's scratch words");
@@ -219,7 +220,7 @@ struct PRun {
       if (c.h_pinned[k] != c.h_pinned[8 + k])
         throw Error(GS_EINVAL, "RCCL ranks disagree on the partitioned run (peers, batch, lazy_gossip, idontwant, "
                                "churn, fragments, seed, schedule, the imported graph, the latency stream or gs_set_peer_delay, "
-                               "the imported mesh)");
+                               "the imported mesh, the imported outages)");
   }
 
   // ---- the u16 latencies of a batch ----
@@ -768,6 +769,8 @@ gs_status run_partitioned(gs_ctx* const* ctxs, uint32_t nctx, gs_comm* comm, con
         c0->fail(GS_EINVAL, "every part needs the same graph (gs_set_topology / gs_set_topology_dials)");
       if (c.mesh_fp != c0->mesh_fp)  // (0: a converged or loaded mesh; an import of the same mesh is not 0)
         c0->fail(GS_EINVAL, "every part needs the same mesh (gs_set_mesh / gs_set_mesh_links in every part, or in none)");
+      if (c.outage_fp != c0->outage_fp)  // (0: the draw; churn batches run message-sharded over one offline table)
+        c0->fail(GS_EINVAL, "every part needs the same outages (gs_set_outages in every part, or in none)");
       part_set(c, comm->nranks, r.me(i));
     });
     if (!comm->local && c0->cfg.device != comm->device)

@@ -1527,7 +1527,7 @@ static void chn_begin(Ctx& c, ChnPrep& cp, uint32_t par, hipStream_t s, uint64_t
   std::vector<uint8_t> ok(B);
   for (uint32_t q = 0; q < B; q++) {
     cq[q] = (uint32_t)(q0[q] - E0);
-    ok[q] = !offline_draw(c.cfg.seed, c.cfg.churn_ppm, c.cfg.churn_down, sched[q].publisher, q0[q]);
+    ok[q] = !c.offline(sched[q].publisher, q0[q]);
   }
   std::vector<uint16_t> alive(64, 0);  // lane j: bit q = lane q*64 + j published (lane l: message l / FP)
   for (uint32_t l = 0; l < B * FP; l++)
@@ -1609,13 +1609,13 @@ static void chn_end(Ctx& c, ChnPrep& cp, hipStream_t to = nullptr) {
         const uint64_t E = E0 + e;
         const uint32_t* er = &ell[((size_t)(E % R) * N + w) * MESH_W];
         uint64_t mm = 0, ge = 0;
-        const bool woff = offline_draw(c.cfg.seed, c.cfg.churn_ppm, c.cfg.churn_down, w, E);
+        const bool woff = c.offline(w, E);
         std::vector<std::pair<uint64_t, uint32_t>> cand;
         for (uint64_t x = row[w]; x < row[w + 1]; x++) {
           bool in = false;
           for (uint32_t j = 0; j < MESH_W; j++) in |= er[j] != EMPTY && (er[j] & 0xFFFFFFu) == col[x];
           if (in) mm |= 1ull << (x - row[w]);
-          else if (!woff && !offline_draw(c.cfg.seed, c.cfg.churn_ppm, c.cfg.churn_down, col[x], E))
+          else if (!woff && !c.offline(col[x], E))
             cand.push_back({rng(c.cfg.seed, P_GOSSIP, w, (uint32_t)E, col[x]), (uint32_t)(x - row[w])});
         }
         std::sort(cand.begin(), cand.end(), [&](const std::pair<uint64_t, uint32_t>& p1, const std::pair<uint64_t, uint32_t>& p2) {

@@ -1010,7 +1010,7 @@ struct Run {
     if (churn) {  // per message: gossip can spread it (publisher online at t_pub, a heartbeat in its lifetime)
       for (uint32_t q = 0; q < B; q++) {
         malive[q] = habs0[q] <= q0v[q] + c.cfg.churn_horizon &&
-                    !offline_draw(c.cfg.seed, c.cfg.churn_ppm, c.cfg.churn_down, sched[r.i0 + q].publisher, q0v[q]);
+                    !c.offline(sched[r.i0 + q].publisher, q0v[q]);
         r.g0 = std::min(r.g0, rel0[q]);
       }
       uint64_t lmin = INF64;

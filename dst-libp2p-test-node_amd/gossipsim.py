@@ -179,6 +179,11 @@ SIGNATURES = {
     "gs_set_mesh": (i32, [ctypes.c_void_p, P(u32), P(u8)]),
     "gs_set_mesh_links": (i32, [ctypes.c_void_p, u64, P(u32), P(u32)]),
     "gs_write_mesh_links": (i32, [ctypes.c_char_p, u32, P(u32), P(u8)]),
+    "gs_set_outages": (i32, [ctypes.c_void_p, u64, P(u32), P(u32), P(u32)]),
+    "gs_clear_outages": (i32, [ctypes.c_void_p]),
+    "gs_get_offline": (i32, [ctypes.c_void_p, u32, u32, P(u64)]),
+    "gs_outage_epochs": (i32, [P(GsConfig), u64, P(u32), P(u64), P(u64), P(u32), P(u32), P(u32), P(u64)]),
+    "gs_read_outages": (i32, [ctypes.c_char_p, P(u32), P(u64), P(u64), u64, P(u64)]),
     "gs_run": (i32, [ctypes.c_void_p, P(GsPublish), u64, P(GsResultSink)]),
     "gs_run_log": (i32, [ctypes.c_void_p, P(GsPublish), u64, TEXT_FN, ctypes.c_void_p, u64]),
     "gs_format_lat_log": (i32, [ctypes.c_void_p, P(GsPublish), u64, P(ctypes.c_uint16), TEXT_FN, ctypes.c_void_p,
@@ -567,6 +572,52 @@ def read_dials(path):
     return d[:n.value], t[:n.value]
 
 
+OUTAGE_FOREVER = 0xFFFFFFFF  # GS_OUTAGE_FOREVER: h_to of a peer that never returns
+OUTAGE_ROW_MAX = 256  # GS_OUTAGE_ROW_MAX
+T_NEVER = 0xFFFFFFFFFFFFFFFF  # t_up_ns of a peer that never returns
+
+
+def read_outages(path):
+    """Outage file, one "peer t_down_ns [t_up_ns]" line per outage -> (peer uint32, t_down_ns, t_up_ns uint64)
+    arrays (gs_read_outages); without a third column t_up_ns is T_NEVER."""
+    n = u64()
+    rc = lib().gs_read_outages(str(path).encode(), None, None, None, 0, ctypes.byref(n))
+    if rc not in (0, GS_ERANGE):
+        raise GossipSimError(rc, "malformed outage list %s: line %d" % (path, n.value))
+    k = max(n.value, 1)
+    p, d, t = np.zeros(k, np.uint32), np.zeros(k, np.uint64), np.zeros(k, np.uint64)
+    rc = lib().gs_read_outages(str(path).encode(), _ptr(p, u32), _ptr(d, u64), _ptr(t, u64), n.value, ctypes.byref(n))
+    if rc:
+        raise GossipSimError(rc, "malformed outage list %s: line %d" % (path, n.value))
+    return p[:n.value], d[:n.value], t[:n.value]
+
+
+def outage_epochs(cfg, peer, t_down_ns, t_up_ns):
+    """Outages in ns as intervals of heartbeat epochs under cfg's heartbeat_ns and hb_phase_ns (a PeerConfig, or
+    anything with these two attributes) -> (peer, h_from, h_to) uint32 arrays (gs_outage_epochs): a peer is
+    offline in epoch h >= 1 iff it is down at the heartbeat that starts it; an outage that covers no heartbeat
+    is left out, t_up_ns == T_NEVER gives h_to == OUTAGE_FOREVER."""
+    if isinstance(cfg, PeerConfig):
+        c = cfg.c
+    else:
+        c = GsConfig()
+        lib().gs_config_default(ctypes.byref(c))
+        c.heartbeat_ns, c.hb_phase_ns = int(cfg.heartbeat_ns), int(cfg.hb_phase_ns)
+    p = np.ascontiguousarray(peer, np.uint32).reshape(-1)
+    d = np.ascontiguousarray(t_down_ns, np.uint64).reshape(-1)
+    t = np.ascontiguousarray(t_up_ns, np.uint64).reshape(-1)
+    if not (p.size == d.size == t.size):
+        raise GossipSimError(GS_EINVAL, "peer, t_down_ns and t_up_ns differ in length")
+    k = max(p.size, 1)
+    po, hf, ht = np.zeros(k, np.uint32), np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+    n = u64()
+    rc = lib().gs_outage_epochs(ctypes.byref(c), p.size, _ptr(np.resize(p, k), u32), _ptr(np.resize(d, k), u64),
+                                _ptr(np.resize(t, k), u64), _ptr(po, u32), _ptr(hf, u32), _ptr(ht, u32), ctypes.byref(n))
+    if rc:
+        raise GossipSimError(rc, "outage_epochs: t_up_ns < t_down_ns, or an epoch past 2^32 - 2")
+    return po[:n.value], hf[:n.value], ht[:n.value]
+
+
 def write_dials(path, row_ptr, col, flags):
     """One "dialer target" line per entry whose flags bit 0 is set, in row order (gs_write_dials)."""
     row, col, flags = _csr_arrays(row_ptr, col, flags)
@@ -772,6 +823,33 @@ class Simulator:
         pad = 1 if a.size == 0 else 0
         self._check(lib().gs_set_mesh_links(self.ctx, a.size, _ptr(np.resize(a, a.size + pad), u32),
                                             _ptr(np.resize(b, b.size + pad), u32)))
+
+    # ---- a caller's outages in place of the churn draw (gs_set_outages) ----
+    def set_outages(self, peer, h_from, h_to):
+        """Who is offline when: peer[i] is offline during the heartbeat epochs h_from[i] <= h < h_to[i]
+        (OUTAGE_FOREVER: it never returns), in any order; no interval is a churn context in which nobody
+        leaves (gs_set_outages). A converge must follow. A refused schedule leaves the simulator as it was."""
+        p = np.ascontiguousarray(peer, np.uint32).reshape(-1)
+        a = np.ascontiguousarray(h_from, np.uint32).reshape(-1)
+        b = np.ascontiguousarray(h_to, np.uint32).reshape(-1)
+        if not (p.size == a.size == b.size):
+            raise GossipSimError(GS_EINVAL, "peer, h_from and h_to differ in length")
+        k = max(p.size, 1)
+        self._check(lib().gs_set_outages(self.ctx, p.size, _ptr(np.resize(p, k), u32), _ptr(np.resize(a, k), u32),
+                                         _ptr(np.resize(b, k), u32)))
+
+    def clear_outages(self):
+        """Back to the churn draw (gs_clear_outages); a converge must follow if a schedule was imported."""
+        self._check(lib().gs_clear_outages(self.ctx))
+
+    def offline(self, h_lo, h_hi):
+        """bool [h_hi - h_lo + 1, peers]: who is offline in each heartbeat epoch of [h_lo, h_hi], from the draw
+        or the imported schedule, as the device's own kernel writes it (gs_get_offline)."""
+        E, W = int(h_hi) - int(h_lo) + 1, (self.peers + 63) // 64
+        bits = np.zeros(max(E, 1) * W, np.uint64)
+        self._check(lib().gs_get_offline(self.ctx, int(h_lo), int(h_hi), _ptr(bits, u64)))
+        b = np.unpackbits(bits.reshape(E, W).view(np.uint8), axis=1, bitorder="little")
+        return b[:, :self.peers].astype(bool)
 
     # ---- publish / run ----
     def publish(self, publisher, msg_size, t_pub_ns):

@@ -28,12 +28,15 @@ void usage() {
           "         [--gml network_topology.gml --yaml shadow.yaml] [--schedule FILE] [--shadowlog PATH] [--metrics PATH]\n"
           "         [--testnode-metrics PATH] [--pubsub-metrics PATH] [--mesh-metrics PATH] [--mesh-series PATH]\n"
           "         [--topology DIALS] [--dump-topology PATH] [--mesh LINKS] [--dump-mesh PATH] [--link-deliveries PATH]\n"
-          "         [--message-costs PATH]\n"
+          "         [--message-costs PATH] [--outages FILE]\n"
           "  --topology imports a dial list (one \"dialer target\" per line) in place of the random dialing;\n"
           "    --dump-topology writes the dial list of the graph the run used\n"
           "  --mesh imports a mesh (one \"a b\" link per line) in place of the heartbeats' converge (not with\n"
           "    --mesh-metrics / --mesh-series, which describe a converge); --dump-mesh writes the links of the mesh\n"
           "    the run used\n"
+          "  --outages imports who is offline when (one \"peer t_down_ns [t_up_ns]\" per line, absolute ns; no third\n"
+          "    column: the peer never returns) in place of the churn draw, converted to heartbeat epochs with the run's\n"
+          "    heartbeat and phase; an error on a run without churn (GS_CHURN_PPM = 0)\n"
           "  --yaml also supplies the injector's -s/-m/-d and start_time unless given on the command line\n"
           "  --device-log writes --latencies from the device-formatted text (gs_run_log), one fwrite per chunk\n"
           "  --testnode-metrics writes the nim node's per-peer delay metrics (dst_testnode_*, gs_set_peer_delay);\n"
@@ -132,7 +135,7 @@ int main(int argc, char** argv) {
   // after the injector sends it (topogen.py:64-69); tx_time is stamped then
   uint64_t http_us = 3000;
   std::string latencies, gml, yaml, shadowlog, metrics, schedule, testnode, pubsub, mesh_metrics, mesh_series;
-  std::string topology, dump_topology, mesh_file, dump_mesh, link_deliveries, message_costs;
+  std::string topology, dump_topology, mesh_file, dump_mesh, link_deliveries, message_costs, outages;
   bool set_size = false, set_msgs = false, set_delay = false, set_t0 = false, device_log = false;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -170,6 +173,7 @@ int main(int argc, char** argv) {
     else if (a == "--dump-mesh") dump_mesh = next();  // the links of the mesh the run used
     else if (a == "--link-deliveries") link_deliveries = next();  // per-link first deliveries (P2, main.rs:252-258)
     else if (a == "--message-costs") message_costs = next();  // what each message cost
+    else if (a == "--outages") outages = next();  // who is offline when, in place of the churn draw
     else if (a == "--schedule") schedule = next();  // rows: t_pub_ns publisher msg_size [frags]
     else { usage(); return 2; }
   }
@@ -209,6 +213,10 @@ int main(int argc, char** argv) {
     bw_dn = bw;
   }
 
+  if (!outages.empty() && !cfg.churn_ppm) {
+    fprintf(stderr, "--outages needs a run with churn (GS_CHURN_PPM != 0; its value is not read with --outages)\n");
+    return 2;
+  }
   gs_ctx* ctx = nullptr;
   if ((st = gs_create(&cfg, &ctx)) != GS_OK) return die(nullptr, st, "gs_create");
   if ((st = gs_set_links(ctx, stages, lat.data(), bw.data(), bw_dn.data(),
@@ -242,6 +250,23 @@ int main(int argc, char** argv) {
     if ((st = gs_get_csr(ctx, row.data(), col.data(), fl.data())) != GS_OK) return die(ctx, st, "gs_get_csr");
     if ((st = gs_write_dials(dump_topology.c_str(), cfg.peers, row.data(), col.data(), fl.data())) != GS_OK)
       return die(ctx, st, "gs_write_dials");
+  }
+  if (!outages.empty()) {  // the outages of a real run (its pods' restarts), or a what-if; before the converge
+    uint64_t rows = 0, kept = 0;
+    st = gs_read_outages(outages.c_str(), nullptr, nullptr, nullptr, 0, &rows);
+    if (st != GS_OK && st != GS_ERANGE) {
+      fprintf(stderr, "malformed outage list %s: line %llu\n", outages.c_str(), (unsigned long long)rows);
+      return die(ctx, st, "gs_read_outages");
+    }
+    std::vector<uint32_t> op(rows + 1), hf(rows + 1), ht(rows + 1);
+    std::vector<uint64_t> td(rows + 1), tu(rows + 1);
+    if ((st = gs_read_outages(outages.c_str(), op.data(), td.data(), tu.data(), rows, &rows)) != GS_OK)
+      return die(ctx, st, "gs_read_outages");
+    if ((st = gs_outage_epochs(&cfg, rows, op.data(), td.data(), tu.data(), op.data(), hf.data(), ht.data(), &kept)) != GS_OK) {
+      fprintf(stderr, "outage list %s: an outage ends before it starts, or lies past epoch 2^32 - 2\n", outages.c_str());
+      return die(ctx, st, "gs_outage_epochs");
+    }
+    if ((st = gs_set_outages(ctx, kept, op.data(), hf.data(), ht.data())) != GS_OK) return die(ctx, st, "gs_set_outages");
   }
   uint32_t epochs = 0;
   if (mesh_file.empty()) {

@@ -31,6 +31,9 @@ graph: --dials replays the connections the run made (gossipsim.read_dials' forma
 --mesh pins the mesh the run ended up with as well (one "a b" link per line, from a
 tracer's Graft / Prune events or the nodes' mesh peers): the comparison is then of the
 dissemination model alone, not of mesh formation plus dissemination.
+--outages replays who was offline when (gossipsim.read_outages' format: the run's pod
+restarts as "peer t_down_ns [t_up_ns]" lines), as a churn run whose offline sets are
+these outages instead of a random draw.
 
 The simulation itself runs on the GPU through the C ABI (gossipsim.Simulator,
 run(summary=True): the percentiles come from the device's gs_msg_summary).
@@ -172,6 +175,16 @@ def form_mesh(sim, mesh=None):
     sim.set_mesh_links(*gossipsim.read_dials(mesh))
 
 
+def import_outages(sim, outages=None):
+    """Who was offline when: the outage file `outages` (one "peer t_down_ns [t_up_ns]" per line, the
+    run's pod restarts), converted to heartbeat epochs with the simulator's heartbeat and phase, in
+    place of the churn draw; without one nothing happens. Before the mesh is formed."""
+    if outages is None:
+        return
+    import gossipsim
+    sim.set_outages(*gossipsim.outage_epochs(sim.cfg, *gossipsim.read_outages(outages)))
+
+
 def run(args):
     import gossipsim
     per = read_latencies(args.latencies)
@@ -182,6 +195,12 @@ def run(args):
     kw = {"peers": args.peers, "fragments": args.fragments, "seed": args.seed, "batch": max(1, len(per))}
     if args.node:
         kw["node"] = gossipsim.NODES[args.node]
+    if args.outages:  # a churn context whose offline sets come from the file: churn_ppm's value is not read,
+        # heartbeat 0 ticks when the nodes start
+        if args.mesh:
+            raise SystemExit("--outages cannot be combined with --mesh: under churn every epoch's mesh comes from "
+                             "the heartbeats")
+        kw.update(churn_ppm=1, hb_phase_ns=gossipsim.SHADOW_START_NS)
     sched = schedule_from_log(per, args.peers, msg_size, args.publisher_id, args.rotation,
                               self_log=args.node == "nim")
     sim = gossipsim.Simulator(**kw)
@@ -191,12 +210,13 @@ def run(args):
         S, bl, bh, ll, lh = [int(x) for x in args.topogen.split(",")]
         sim.set_topogen_links(S, bl, bh, ll, lh, shortest=args.shortest)
     connect(sim, args.dials)
+    import_outages(sim, args.outages)
     form_mesh(sim, args.mesh)
     res = sim.run(sched, collect=False, summary=True)
     rep = compare(summarize(per), sim_summary(res["summary"], sched), args.tol)
     rep["config"] = {"peers": args.peers, "msg_size": msg_size, "fragments": args.fragments, "seed": args.seed,
                      "links": args.gml or args.topogen, "latencies": args.latencies, "dials": args.dials,
-                     "mesh": args.mesh}
+                     "mesh": args.mesh, "outages": args.outages}
     return rep
 
 
@@ -214,6 +234,8 @@ def main(argv=None):
     ap.add_argument("--dials", help="dial list file (\"dialer target\" per line): replay that graph instead of "
                                     "connect_gossipsub_peers()")
     ap.add_argument("--mesh", help="mesh link file (\"a b\" per line): run on that mesh instead of mesh_converge()")
+    ap.add_argument("--outages", help="outage file (\"peer t_down_ns [t_up_ns]\" per line, absolute ns): who was "
+                                      "offline when, as a churn run with these outages in place of the draw")
     ap.add_argument("--node", choices=("rust", "go", "nim"), default="rust")
     ap.add_argument("--publisher-id", type=int, help="run.sh publisher_id (when the log cannot name one)")
     ap.add_argument("--rotation", type=int, default=0, help="run.sh publisher_rotation")

@@ -474,6 +474,57 @@ gs_status gs_set_mesh_links(struct gs_ctx* ctx, uint64_t n_links, const uint32_t
  * gs_write_dials, read back by gs_read_dials. count may be NULL as for gs_set_mesh. */
 gs_status gs_write_mesh_links(const char* path, uint32_t peers, const uint32_t* mesh, const uint8_t* count);
 
+/* A caller's outages in place of the churn draw (DESIGN.md §2.8 "A caller's outages"): who
+ * is offline when, as intervals (peer[i], h_from[i], h_to[i]) in heartbeat epochs. The peer
+ * is offline during the epochs h_from <= h < h_to; h_to == GS_OUTAGE_FOREVER: it never
+ * returns. Epoch 0 has nobody offline (h_from >= 1). The schedule is a function of the set
+ * of intervals: the list's order shows in nothing. Intervals of one peer may touch (their
+ * union) but not share an epoch. n == 0 is the empty schedule: a churn context in which
+ * nobody ever leaves. churn_ppm != 0 remains what makes a context a churn context
+ * (GS_ESTATE otherwise); while a schedule is imported, its value and churn_down are not
+ * read, churn_horizon applies as before.
+ * gs_set_outages stands before gs_mesh_converge and may be repeated at any time: an accepted
+ * schedule un-builds the mesh (a converge must follow; a run before it returns GS_ESTATE),
+ * restarts the epoch chain and the ring, and leaves the mesh-event getters at GS_ESTATE until
+ * that converge. A refused one (GS_EINVAL for peer >= peers, h_from == 0, h_from >= h_to or
+ * two intervals of one peer that share an epoch; GS_EUNSUPPORTED for n >= 2^32 or more than
+ * GS_OUTAGE_ROW_MAX intervals of one peer) leaves the context as it was; gs_last_error names
+ * the kind of defect and the smallest interval (or peer) index that has it.
+ * gs_clear_outages returns to the draw, with the same invalidation; without an import it
+ * does nothing and returns GS_OK.
+ * gs_save_state returns GS_EUNSUPPORTED while a schedule is imported (the file does not
+ * carry it). Partitioned runs need the same schedule in every context, or none (GS_EINVAL
+ * before any batch otherwise). */
+#define GS_OUTAGE_FOREVER 0xFFFFFFFFu
+#define GS_OUTAGE_ROW_MAX 256u
+gs_status gs_set_outages(struct gs_ctx* ctx, uint64_t n, const uint32_t* peer,
+                         const uint32_t* h_from, const uint32_t* h_to);
+gs_status gs_clear_outages(struct gs_ctx* ctx);
+/* The offline bitsets of epochs [h_lo, h_hi] from whichever source is active, the draw or
+ * the imported schedule, written by the kernel that feeds the epoch chain:
+ * bits[(h_hi - h_lo + 1)][(peers + 63) / 64], bit u % 64 of word u / 64 = peer u is offline.
+ * Bits at and past `peers` are 0, and epoch 0 is all 0. GS_ESTATE when churn_ppm == 0,
+ * GS_EINVAL when h_hi < h_lo. */
+gs_status gs_get_offline(struct gs_ctx* ctx, uint32_t h_lo, uint32_t h_hi, uint64_t* bits);
+/* Host only. The times of a trace as epochs: a peer is offline in epoch h >= 1 iff it is
+ * down at the heartbeat that starts the epoch, t_down <= hb_phase + h * heartbeat < t_up
+ * (cfg's heartbeat_ns and hb_phase_ns; the rule is build-defined, as churn is). So
+ * h_from = max(1, ceil((t_down - hb_phase) / heartbeat)), 1 when t_down <= hb_phase, and
+ * h_to = ceil((t_up - hb_phase) / heartbeat), GS_OUTAGE_FOREVER when t_up == UINT64_MAX.
+ * An outage that covers no heartbeat is left out; *n_out counts the ones kept, in input
+ * order (the output arrays hold n entries and may be the input's). Outages of one peer that
+ * are disjoint in time can touch in epochs but never overlap. GS_EINVAL for t_up < t_down,
+ * GS_ERANGE for an epoch past 2^32 - 2. */
+gs_status gs_outage_epochs(const gs_config* cfg, uint64_t n, const uint32_t* peer,
+                           const uint64_t* t_down_ns, const uint64_t* t_up_ns,
+                           uint32_t* peer_out, uint32_t* h_from, uint32_t* h_to, uint64_t* n_out);
+/* Host only. An outage list as text: one "peer t_down_ns [t_up_ns]" line per outage, a
+ * missing third column meaning the peer never returns (t_up = UINT64_MAX); '#' comments,
+ * blank lines and the cap contract as gs_read_dials. A malformed line is GS_EINVAL with
+ * *n = the number of that line, counted from 1 (0: the file cannot be opened). */
+gs_status gs_read_outages(const char* path, uint32_t* peer, uint64_t* t_down_ns,
+                          uint64_t* t_up_ns, uint64_t cap, uint64_t* n);
+
 /* Simulate n_msgs publishes (replaces publish_new_message + the receive /
  * forward / reassembly loop, main.rs:79-143,519-528). Results go to `sink`
  * (may be NULL: device-resident run, counters only). */

@@ -145,6 +145,15 @@ extern "C" {
     pub fn gs_set_mesh(ctx: *mut gs_ctx, mesh: *const u32, count: *const u8) -> gs_status;
     pub fn gs_set_mesh_links(ctx: *mut gs_ctx, n_links: u64, a: *const u32, b: *const u32) -> gs_status;
     pub fn gs_write_mesh_links(path: *const c_char, peers: u32, mesh: *const u32, count: *const u8) -> gs_status;
+    pub fn gs_set_outages(ctx: *mut gs_ctx, n: u64, peer: *const u32, h_from: *const u32, h_to: *const u32)
+                          -> gs_status;
+    pub fn gs_clear_outages(ctx: *mut gs_ctx) -> gs_status;
+    pub fn gs_get_offline(ctx: *mut gs_ctx, h_lo: u32, h_hi: u32, bits: *mut u64) -> gs_status;
+    pub fn gs_outage_epochs(cfg: *const gs_config, n: u64, peer: *const u32, t_down_ns: *const u64,
+                            t_up_ns: *const u64, peer_out: *mut u32, h_from: *mut u32, h_to: *mut u32,
+                            n_out: *mut u64) -> gs_status;
+    pub fn gs_read_outages(path: *const c_char, peer: *mut u32, t_down_ns: *mut u64, t_up_ns: *mut u64, cap: u64,
+                           n: *mut u64) -> gs_status;
     pub fn gs_get_mesh(ctx: *mut gs_ctx, mesh: *mut u32, count: *mut u8) -> gs_status;
     pub fn gs_run(ctx: *mut gs_ctx, sched: *const gs_publish, n: u64, sink: *const gs_result_sink) -> gs_status;
     pub fn gs_run_log(ctx: *mut gs_ctx, sched: *const gs_publish, n: u64, on_text: gs_text_fn, user: *mut c_void,
